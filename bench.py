@@ -12,9 +12,14 @@ latents of a 4096*N-output model (weak scaling, configs[3] at N=8); the only col
 all-reduce of the scalar NLL.  Other configs: --config c1 | c2 | c3f64 | c2d6 | c5 | c4 | c3learn (configs[2] with its outer loop: one
 objective evaluation of the online learner, MOIHGP::update + the windowed NLL/gradient sweep, at M = L = 4096).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c1|c2|c3f64|c2d6|c3d6|c3d6f64|c5|c4|c3learn|c3grad|c5grad] [--no-cpu]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c1|c2|c3f64|c2d6|c3d6|c3d6f64|c5|c4|c3learn|c3grad|c5grad]
+                    [--dump-outputs DIR] [--full [--no-cpu] [--no-cold] [--no-others]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps, writes its outputs (--dump-outputs) and prints the result line.  Everything else
+the line can carry -- the kernel-exact and roofline figures, the cold-stream leg, the other BASELINE configurations, the CPU baseline
+and the parity figures against the CPU oracle -- takes runs of its own and is measured only with --full.
 
 `python bench.py --gpus N` with N > 1 and no launcher around it (WORLD_SIZE unset) starts the N ranks itself: the parent, which makes
 no GPU call, runs `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a CHILD process (never exec in place), relays
@@ -63,6 +68,30 @@ ORACLE_KERNEL = {"Matern52ss": "Matern52", "Matern32": "Matern32"}      # produc
 HBM_PEAK_GBPS = 8000.0        # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy)
 HBM_COPY_GBPS = 6290.0
 SEED = 20260101
+DUMP_BYTES = 48 * 2 ** 20     # --dump-outputs: at most this much in all (over all ranks), inside the 64 MB allowed with room for the .npy headers
+
+
+def dump_outputs(dirname, arrays, budget=DUMP_BYTES, suffix=""):
+    """--dump-outputs: write what the timed path returned in its last step as DIR/<name><suffix>.npy, float32 or float64 as computed, so
+    that two builds can be compared output for output.  The budget is shared out smallest array first; an array larger than its share is
+    cut to a fixed sample of its rows (leading index), drawn from a seeded generator: the same rows in every run with the same arguments."""
+    os.makedirs(dirname, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: kv[1].nelement() * kv[1].element_size() if torch.is_tensor(kv[1]) else np.asarray(kv[1]).nbytes)
+    left = budget
+    for i, (name, a) in enumerate(items):
+        if not torch.is_tensor(a):
+            a = torch.from_numpy(np.asarray(a))
+        assert a.dtype in (torch.float32, torch.float64), (name, a.dtype)
+        a = a.detach().reshape((-1,) if a.dim() == 0 else a.shape)
+        share = left // (len(items) - i)
+        row_bytes = max(1, a[0].nelement()) * a.element_size()
+        if a.shape[0] * row_bytes > share:
+            n = max(1, share // row_bytes)
+            rows = np.sort(np.random.default_rng(SEED + 3).choice(a.shape[0], n, replace=False))
+            a = a[torch.from_numpy(rows).to(a.device)]
+        h = a.cpu().numpy()
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), h)
+        left -= h.nbytes
 
 
 def synth_params(L, lo, rng, kernel="Matern52ss"):
@@ -222,11 +251,13 @@ def run_c1(args, rank, world):
 
     for _ in range(max(1, min(args.warmup, 2))):
         one_pass()
-    steps = max(1, min(args.steps, 20))
+    steps = max(1, args.steps)
     t0 = time.perf_counter()
     for _ in range(steps):
         xT, Yhat = one_pass()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"yhat": Yhat, "x": xT})
     per_call = elapsed / (steps * T)
     out = {
         "metric": "Kalman steps/sec (M outputs x T ticks) + NLL rel-err vs CPU oracle",
@@ -238,7 +269,7 @@ def run_c1(args, rank, world):
                      "traffic": None, "kernel": "fused_step_kernel", "kernel_ms": None, "call_us": per_call * 1e6,
                      "note": "launch-latency bound by construction (64 bytes per call); see the batched entries for throughput"},
     }
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         from oracle import cref
         ref = cref.GP(0.1, M, L, "Matern32")
         ref.update(gp.params)
@@ -256,7 +287,7 @@ def run_c1(args, rank, world):
     print(json.dumps(out), flush=True)
 
 
-def learn_row(steps, warmup, cpu=True, windows=(16, 128)):
+def learn_row(steps, warmup, cpu=True, windows=(16, 128), outputs=None):
     """BASELINE.json configs[2] as worded: "M=4096 outputs, T=10000, Matern-5/2, fp32, online-learning L-BFGS outer loop".  The
     optimiser stays on the host (north_star); what it calls per line-search point is ONE objective evaluation
     (moihgp_online.h:40-72, online_learning.py:74-98):  MOIHGP::update(params) -- polar factor of the M x L mixing + IHGP::update of
@@ -276,7 +307,7 @@ def learn_row(steps, warmup, cpu=True, windows=(16, 128)):
     p[M * L + L + 1:] = synth_params(L, 0, rng).ravel()
     d = gp.igp_dim
     x = np.zeros((L, d)); dx = np.zeros((L, 3, d))
-    steps = max(1, min(steps, 10)); warm = max(1, min(warmup, 2))
+    steps = max(1, steps); warm = max(1, min(warmup, 2))
     dev = torch.device("cuda", torch.cuda.current_device())
     have_dev = hasattr(gp, "update_dev")
     if have_dev:
@@ -310,6 +341,8 @@ def learn_row(steps, warmup, cpu=True, windows=(16, 128)):
                                               kalman_steps_per_s=L * W / (t_upd + t_ev), loss=float(loss_dev.item()),
                                               grad_max_abs_diff_vs_host_path=float((g_dev.cpu().numpy() - grad).__abs__().max()))
     W = windows[-1]
+    if outputs is not None:                 # what the timed evaluations of the reported form (the last window) return
+        outputs.update(dict(loss=loss_dev, grad=g_dev) if have_dev else dict(loss=np.array([loss]), grad=grad))
     # roofline of the dominant part: the fp64 MFMA GEMMs of the polar factor (Newton-Schulz: per step one symmetric Gram 2 M L^2 / 2
     # upper tiles + one product 2 M L^2) and of the window (projection, U U^T y, U-gradient: 3 x 2 W M L)
     ns_steps = max(1, int(load_library().moihgp_polar_iterations(gp.handle)))   # what the last update() actually took
@@ -389,7 +422,7 @@ def loop_row(ticks=3, W=16, threading=True):
     }
 
 
-def grad_row(config, steps, warmup, cpu=True):
+def grad_row(config, steps, warmup, cpu=True, outputs=None):
     """Mode G of SURVEY 8(d) over whole streams: the sensitivity / gradient sweep (ihgp.h:37-57 + :212-222 per tick: step with
     sensitivities, NLL and its gradient w.r.t. the latent's hyper-parameters), resident streams, one GPU.  c3grad: C3's shape
     (4096 x 10^4, Matern-5/2, d = 3, P = 3, fp32); c5grad: C5's (d = 12 stacked, P = 9, fp64).  A step = one sweep."""
@@ -408,6 +441,8 @@ def grad_row(config, steps, warmup, cpu=True):
         r = bank.grad(Ty, T=T, want_yhat=False)
     torch.cuda.synchronize()
     sec = (time.perf_counter() - t0) / steps
+    if outputs is not None:
+        outputs.update({k: v for k, v in r.items() if v is not None})
     steps_per_s = L * T / sec
     peak = 157.3 if dtype == torch.float32 else 78.6
     ref_flops = 2 * d * d + 4 * d + 5 + P * (4 * d * d + 6 * d + 8)              # SURVEY 8(d), mode G, the reference's dense form
@@ -791,9 +826,14 @@ def main():
     ap.add_argument("--rotate", action="store_true",
                     help="every pass of every loop (warm-up, timed, bracketed) sweeps the NEXT of enough distinct stream pairs that nothing it reads is still "
                          "on chip: a run whose kernel trace holds cold launches only (profiles/: the rocprofv3 summary that `roofline.frac` is checked against)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline / parity leg")
-    ap.add_argument("--no-cold", action="store_true", help="skip the cold-stream leg (roofline.frac_cold): profiled runs, so that a kernel trace holds the timed launches only")
-    ap.add_argument("--no-others", action="store_true", help="skip the other BASELINE configurations that the default line carries in other_configs")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, measure what the line carries beyond its headline: kernel-exact and roofline figures, the cold-stream leg, "
+                         "the other BASELINE configurations (other_configs), the CPU baseline and the parity figures against the CPU oracle")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline / parity leg")
+    ap.add_argument("--no-cold", action="store_true", help="with --full: skip the cold-stream leg (roofline.frac_cold): profiled runs, so that a kernel trace holds the timed launches only")
+    ap.add_argument("--no-others", action="store_true", help="with --full: skip the other BASELINE configurations that the line carries in other_configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (48 MiB at most in all: larger outputs as a fixed, seeded sample of rows)")
     ap.add_argument("--sync-allreduce", action="store_true", help="N > 1: make every pass wait for its own NLL all-reduce (no overlap with the next sweep)")
     args = ap.parse_args()
     if args.warmup is None:
@@ -839,15 +879,23 @@ def main():
 
     if args.config == "c1":
         return run_c1(args, rank, world)
-    if args.config == "c3learn":
-        print(json.dumps(learn_row(args.steps, args.warmup, cpu=not args.no_cpu)), flush=True)
-        return 0
-    if args.config in ("c3grad", "c5grad"):
-        print(json.dumps(grad_row(args.config, args.steps, args.warmup, cpu=not args.no_cpu)), flush=True)
+    cpu = args.full and not args.no_cpu
+    if args.config in ("c3learn", "c3grad", "c5grad"):
+        outputs = {} if args.dump_outputs else None
+        if args.config == "c3learn":
+            out = learn_row(args.steps, args.warmup, cpu=cpu, outputs=outputs)
+        else:
+            out = grad_row(args.config, args.steps, args.warmup, cpu=cpu, outputs=outputs)
+        if outputs:
+            dump_outputs(args.dump_outputs, outputs)
+        print(json.dumps(out), flush=True)
         return 0
     if args.config == "c3loop":
-        out = loop_row(ticks=max(1, min(args.steps, 10)), threading=True)
-        out["threading_off"] = loop_row(ticks=max(1, min(args.steps, 3)), threading=False)["learner"]
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: --config c3loop times a separate C++ program (tools/cxx/learner_bench.cpp) whose outputs bench.py does not receive")
+        out = loop_row(ticks=max(1, args.steps), threading=True)
+        if args.full:
+            out["threading_off"] = loop_row(ticks=max(1, min(args.steps, 3)), threading=False)["learner"]
         print(json.dumps(out), flush=True)
         return 0
 
@@ -958,75 +1006,44 @@ def main():
     sync()
     elapsed = time.perf_counter() - t0
     elapsed = max_over_ranks(elapsed, device="cpu" if rehearsal else device)
-    # kernel-exact durations, OUTSIDE the timed region: a second loop of the same passes with a HIP event pair attached to every filter
-    # dispatch (hipExtLaunchKernel, on the launch stream)
-    kpasses = max(1, min(KERNEL_PASSES, args.steps))
-    bank.profile_enable(kpasses * nslab, stride=PROFILE_STRIDE)
-    tk0 = time.perf_counter()
-    for k in range(kpasses):
-        total_k = one_pass(reduce=lambda t: t)
-    sync()
-    ms_per_step_bracketed = (time.perf_counter() - tk0) / kpasses * 1e3
-    kern_samples = bank.profile_read()
-    kern_ms = float(np.mean(kern_samples))                          # mean over the launches of the bracketed loop
-    bank.profile_enable(0)
+    if args.dump_outputs:
+        # what a caller of the timed path receives from its last step: filtered means (series-major), final state, per-latent NLL, NLL total
+        if nslab == 1:
+            y_last = rot_pairs[(pass_no[0] - 1) % len(rot_pairs)][1]
+            y_last, nll_last = (untile_stream(y_last, T) if tiled else y_last), nll
+        else:
+            y_last = torch.cat([(untile_stream(yt_slabs[k], Ty_slabs[k].shape[1]) if tiled else yhat_slabs[k])[:, :Ty_slabs[k].shape[1]]
+                                for k in range(nslab)], dim=1)
+            nll_last = nll_acc
+        dump_outputs(args.dump_outputs, {"yhat": y_last[:, :T], "x": x, "nll": nll_last, "nll_total": total},
+                     budget=DUMP_BYTES // world, suffix=f"_rank{rank}" if world > 1 else "")
 
-    # N > 1 on real GPUs: BASELINE.json configs[3] as worded (T = 10^5 in slabs, the NLL all-reduced once per pass) rides along, every rank
-    # taking part, so that a scaling line also shows the collective at work on that configuration
     c4_multi = None
-    if world > 1 and not rehearsal and not stub and args.config == "c3" and not args.no_others:
-        try:
-            c4_multi = slab_row(device, passes=3, warm=1, world=world, rank=rank, reduce=allreduce_nll)
-        except Exception as e:
-            c4_multi = {"error": str(e)}
+    if args.full:
+        # kernel-exact durations, OUTSIDE the timed region: a second loop of the same passes with a HIP event pair attached to every filter
+        # dispatch (hipExtLaunchKernel, on the launch stream)
+        kpasses = max(1, min(KERNEL_PASSES, args.steps))
+        bank.profile_enable(kpasses * nslab, stride=PROFILE_STRIDE)
+        tk0 = time.perf_counter()
+        for k in range(kpasses):
+            total_k = one_pass(reduce=lambda t: t)
+        sync()
+        ms_per_step_bracketed = (time.perf_counter() - tk0) / kpasses * 1e3
+        kern_samples = bank.profile_read()
+        kern_ms = float(np.mean(kern_samples))                          # mean over the launches of the bracketed loop
+        bank.profile_enable(0)
+
+        # N > 1 on real GPUs: BASELINE.json configs[3] as worded (T = 10^5 in slabs, the NLL all-reduced once per pass) rides along, every rank
+        # taking part, so that a scaling line also shows the collective at work on that configuration
+        if world > 1 and not rehearsal and not stub and args.config == "c3" and not args.no_others:
+            try:
+                c4_multi = slab_row(device, passes=3, warm=1, world=world, rank=rank, reduce=allreduce_nll)
+            except Exception as e:
+                c4_multi = {"error": str(e)}
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = Lglobal * T / (elapsed / args.steps)
-        es = 4 if dtype == torch.float32 else 8
-        alg_bytes = 2 * es * L * min(slab, T)           # per LAUNCH; SURVEY 8d mode F: read Ty + write Tyhat = 2*s B per Kalman step
-        achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
-        traffic, traffic_source = pmc_traffic(args.config)
-        cold = {}
-        other_layout = None
-        if nslab == 1 and not args.no_cold and not stub:
-            cold = cold_leg(bank, Tt if tiled else Ty, yt if tiled else yhat, x, x_zero, nll, T, alg_bytes, es, tiled=tiled)
-            if can_tile and world == 1:
-                # the same sweep in the OTHER layout: kernel durations only (resident: bracketed launches with the total between them, as the
-                # headline's second loop; cold: rotating pairs)
-                try:
-                    if tiled:
-                        o_in, o_out = Ty, yhat
-                    else:
-                        from multioutputihgp_amd.streams import tile_stream
-                        o_in = tile_stream(Ty, T); o_out = torch.empty_like(o_in)
-                    bank.profile_enable(20)
-                    for _ in range(20):
-                        if tiled:
-                            bank.filter(o_in, T=T, x=x, x_start=x_zero, yhat=o_out, nll=nll, nll_total=tot_ring[0])
-                        else:
-                            bank.filter_tiled(o_in, T, x=x, x_start=x_zero, yhat=o_out, nll=nll, nll_total=tot_ring[0])
-                    o_ms = float(np.mean(bank.profile_read()))
-                    o_cold = cold_leg(bank, o_in, o_out, x, x_zero, nll, T, alg_bytes, es, tiled=not tiled)
-                    bank.profile_enable(0)
-                    other_layout = {"layout": "series-major [L][ld]" if tiled else "segment-major [T/SEG][L][SEG]",
-                                    "kernel_ms_resident": o_ms, "frac_resident": alg_bytes / (o_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
-                                    "kernel_ms_cold": o_cold.get("kernel_ms_cold"), "frac_cold": o_cold.get("frac_cold")}
-                except Exception as e:
-                    other_layout = {"error": str(e)}
-        # roofline.frac is the HBM-honest figure.  One resident stream pair swept again and again is partly served by the 256 MiB Infinity
-        # Cache (C3's input is 164 MB), so `frac` / `achieved` / `kernel_ms` are those of the COLD leg -- the same launch rotating over
-        # enough distinct stream pairs that nothing it reads is still on chip -- and the resident figures are reported next to them.  A
-        # slab sweep (c4) is cold by construction (3.3 GB working set); with --no-cold the resident figure stands in and says so.
-        if cold.get("frac_cold") is not None:
-            head_ms, head_kind = cold["kernel_ms_cold"], "cold: " + cold["cold_note"]
-        elif nslab > 1:
-            head_ms, head_kind = kern_ms, f"cold by construction: {nslab} slabs of one {2 * es * L * T / 2 ** 30:.1f} GiB working set"
-        elif args.rotate and len(rot_pairs) > 1:
-            head_ms, head_kind = kern_ms, f"cold: --rotate, every pass of the run sweeps the next of {len(rot_pairs)} distinct stream pairs"
-        else:
-            head_ms, head_kind = kern_ms, "RESIDENT stream (cold leg skipped): cache-assisted when the input fits the 256 MiB Infinity Cache"
-        head_achieved = alg_bytes / (head_ms * 1e-3) / 1e9
         out = {
             "metric": "Kalman steps/sec (M outputs x T ticks) + NLL rel-err vs CPU oracle",
             "value": value, "unit": "Kalman steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -1034,22 +1051,6 @@ def main():
             "dtype": "f32" if dtype == torch.float32 else "f64", "data": "synthetic",
             "config": {"workload": desc, "latents_per_gpu": Lg_per, "latents_total": Lglobal, "ticks": T, "state_dim": bank.d,
                        "layout": ("segment-major [ceil(T/SEG)][L][SEG], SEG = 4 KB of ticks" if tiled else "series-major [L][ld]") + ", HBM-resident", "sharding": f"latents x{world}, NLL scalar all-reduce per pass" + ("" if world == 1 else (" (stream-ordered)" if args.sync_allreduce else " (overlapped with the next pass)"))},
-            "roofline": {"bound": "hbm", "achieved": head_achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": head_achieved / HBM_PEAK_GBPS,
-                         "frac_is": head_kind,
-                         "traffic": traffic, "traffic_source": traffic_source,
-                         "kernel": filter_kernel_name(bank, L, T, dtype), "kernel_ms": head_ms,
-                         "frac_resident": achieved / HBM_PEAK_GBPS, "achieved_resident": achieved, "kernel_ms_resident": kern_ms,
-                         "kernel_ms_from": f"HIP event pairs on every launch of a second loop of {kpasses} passes behind the timed region "
-                                           f"({len(kern_samples)} launches; that loop's own wall time: {ms_per_step_bracketed:.4f} ms per pass)",
-                         "algorithmic_bytes_per_launch": alg_bytes, "frac_of_measured_copy_peak": head_achieved / HBM_COPY_GBPS,
-                         # what a plain copy with this sweep's access pattern reaches on this chip (tools/micro/rows_copy.hip, profiles/r04/
-                         # rows_copy_access_pattern.log: 4096 row streams 40 KB apart, one wavefront each): the layout's own ceiling
-                         "access_pattern_copy_ceiling_GBps": ({"resident": 6900.0, "cold": 5940.0} if tiled else {"resident": 6820.0, "cold": 5250.0}),
-                         "access_pattern_copy_ceiling_source": "profiles/r04/rows_copy_access_pattern.log (one wavefront per latent, 4 KB per step, this layout)",
-                         "other_layout": other_layout,
-                         # the other wall (mode F is 2 d^2 + 2 d flop per step; the d = 12 fp64 configuration sits on this one)
-                         "vector_alu": valu_side(bank.d, dtype, L * min(slab, T) / (kern_ms * 1e-3))},
-            "ms_per_step_with_event_pairs": ms_per_step_bracketed,
             "nll_total": float(total.item()),
         }
         if multi and not rehearsal:
@@ -1059,74 +1060,136 @@ def main():
             out["collective"] = {"backend": dist.get_backend(), "world": dist.get_world_size(), "op": "rehearsal"}
         if stub:
             out["rehearsal"] = "BENCH_REHEARSAL=stub: the sweep is a stub on the CPU (launch / rank / reduction logic only): NOT a measurement"
-            out["roofline"]["frac"] = None; out["roofline"]["achieved"] = None
         elif rehearsal:
             out["rehearsal"] = "all ranks on one GPU, gloo exchange: numbers are not comparable"
         if force_dist:
             out["forced_dist"] = f"process group built for {world} rank(s) (backend {dist.get_backend()}): every pass ran its all-reduce"
-        for k_, v_ in cold.items():
-            out["roofline"].setdefault(k_, v_)
-        if c4_multi is not None:
-            out["other_configs"] = {"c4": c4_multi}
-        if world == 1 and not args.no_cpu and not stub:
-            if not args.no_others and not force_dist:
-                # the other single-GPU rows of BASELINE.json / SURVEY 8, measured in the same run: the other filter shapes (kernel-exact
-                # events + wall clock + cold leg), the gradient sweeps (mode G) and configs[2]'s objective evaluation
-                others = {}
-                for name in sorted(CONFIGS):
-                    if name == args.config or name in SLAB:
-                        continue
-                    others[name] = filter_row(name, device)
-                for name in ("c3grad", "c5grad"):
-                    g = grad_row(name, 10, 2, cpu=False)
-                    others[name] = {"workload": g["config"]["workload"], "state_dim": g["config"]["state_dim"], "dtype": g["dtype"], "ms_per_step": g["ms_per_step"],
-                                    "value": g["value"], "kernel": g["roofline"]["kernel"], "kernel_ms": g["roofline"]["kernel_ms"],
-                                    "kernel_ms_from": g["roofline"]["kernel_ms_from"], "bound": "valu", "achieved_TFLOPs": g["roofline"]["achieved"],
-                                    "peak_TFLOPs": g["roofline"]["peak"], "frac": g["roofline"]["frac"], "flops_per_step": g["roofline"]["flops_per_step"],
-                                    "flop_count": g["roofline"]["flop_count"]}
-                for nm, dt_ in (("c3e2e", torch.float32), ("c3e2e_f64", torch.float64)):
+        if args.full:
+            es = 4 if dtype == torch.float32 else 8
+            alg_bytes = 2 * es * L * min(slab, T)           # per LAUNCH; SURVEY 8d mode F: read Ty + write Tyhat = 2*s B per Kalman step
+            achieved = alg_bytes / (kern_ms * 1e-3) / 1e9
+            traffic, traffic_source = pmc_traffic(args.config)
+            cold = {}
+            other_layout = None
+            if nslab == 1 and not args.no_cold and not stub:
+                cold = cold_leg(bank, Tt if tiled else Ty, yt if tiled else yhat, x, x_zero, nll, T, alg_bytes, es, tiled=tiled)
+                if can_tile and world == 1:
+                    # the same sweep in the OTHER layout: kernel durations only (resident: bracketed launches with the total between them, as the
+                    # headline's second loop; cold: rotating pairs)
                     try:
-                        others[nm] = e2e_row(device, dt_)
-                    except Exception as e:         # (context rows: never let one take the headline down)
-                        others[nm] = {"error": str(e)}
-                try:
-                    others["c4"] = slab_row(device)
-                except Exception as e:
-                    others["c4"] = {"error": str(e)}
-                try:
-                    others["c5gaps"] = gaps_row(device)            # configs[4]'s shape with 1 % of the ticks missing, fp64 and fp32
-                except Exception as e:
-                    others["c5gaps"] = {"error": str(e)}
-                try:
-                    lr = learn_row(3, 1, cpu=False, windows=(128,))
-                    others["c3learn"] = {"workload": lr["config"]["workload"], "dtype": "f64", "ms_per_step": lr["ms_per_step"], "value": lr["value"],
-                                         "bound": "mfma", "achieved_TFLOPs": lr["roofline"]["achieved"], "peak_TFLOPs": 78.6, "frac": lr["roofline"]["frac"],
-                                         "update_ms": lr["roofline"]["update_ms"], "window_eval_ms": lr["roofline"]["window_eval_ms"],
-                                         "host_path_evaluation_ms": lr["roofline"]["host_path_evaluation_ms"], "note": lr["roofline"]["note"]}
-                except Exception as e:             # (a context line: never let it take the headline down)
-                    others["c3learn"] = {"error": str(e)}
-                try:
-                    lo = loop_row(ticks=3, threading=True)
-                    others["c3loop"] = {"workload": lo["config"]["workload"], "dtype": "f64", "ms_per_step": lo["ms_per_step"], "value": lo["value"],
-                                        "objective_evaluations_per_tick": lo["learner"]["objective_evaluations_per_tick"],
-                                        "lbfgs_iterations_per_tick": lo["learner"]["lbfgs_iterations_per_tick"],
-                                        "ms_per_objective_evaluation_incl_optimiser": lo["ms_per_objective_evaluation_incl_optimiser"]}
-                except Exception as e:
-                    others["c3loop"] = {"error": str(e)}
-                out["other_configs"] = others
-            if tiled:                                   # the parity leg reads series-major means
+                        if tiled:
+                            o_in, o_out = Ty, yhat
+                        else:
+                            from multioutputihgp_amd.streams import tile_stream
+                            o_in = tile_stream(Ty, T); o_out = torch.empty_like(o_in)
+                        bank.profile_enable(20)
+                        for _ in range(20):
+                            if tiled:
+                                bank.filter(o_in, T=T, x=x, x_start=x_zero, yhat=o_out, nll=nll, nll_total=tot_ring[0])
+                            else:
+                                bank.filter_tiled(o_in, T, x=x, x_start=x_zero, yhat=o_out, nll=nll, nll_total=tot_ring[0])
+                        o_ms = float(np.mean(bank.profile_read()))
+                        o_cold = cold_leg(bank, o_in, o_out, x, x_zero, nll, T, alg_bytes, es, tiled=not tiled)
+                        bank.profile_enable(0)
+                        other_layout = {"layout": "series-major [L][ld]" if tiled else "segment-major [T/SEG][L][SEG]",
+                                        "kernel_ms_resident": o_ms, "frac_resident": alg_bytes / (o_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
+                                        "kernel_ms_cold": o_cold.get("kernel_ms_cold"), "frac_cold": o_cold.get("frac_cold")}
+                    except Exception as e:
+                        other_layout = {"error": str(e)}
+            # roofline.frac is the HBM-honest figure.  One resident stream pair swept again and again is partly served by the 256 MiB Infinity
+            # Cache (C3's input is 164 MB), so `frac` / `achieved` / `kernel_ms` are those of the COLD leg -- the same launch rotating over
+            # enough distinct stream pairs that nothing it reads is still on chip -- and the resident figures are reported next to them.  A
+            # slab sweep (c4) is cold by construction (3.3 GB working set); with --no-cold the resident figure stands in and says so.
+            if cold.get("frac_cold") is not None:
+                head_ms, head_kind = cold["kernel_ms_cold"], "cold: " + cold["cold_note"]
+            elif nslab > 1:
+                head_ms, head_kind = kern_ms, f"cold by construction: {nslab} slabs of one {2 * es * L * T / 2 ** 30:.1f} GiB working set"
+            elif args.rotate and len(rot_pairs) > 1:
+                head_ms, head_kind = kern_ms, f"cold: --rotate, every pass of the run sweeps the next of {len(rot_pairs)} distinct stream pairs"
+            else:
+                head_ms, head_kind = kern_ms, "RESIDENT stream (cold leg skipped): cache-assisted when the input fits the 256 MiB Infinity Cache"
+            head_achieved = alg_bytes / (head_ms * 1e-3) / 1e9
+            out["roofline"] = {"bound": "hbm", "achieved": head_achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": head_achieved / HBM_PEAK_GBPS,
+                               "frac_is": head_kind,
+                               "traffic": traffic, "traffic_source": traffic_source,
+                               "kernel": filter_kernel_name(bank, L, T, dtype), "kernel_ms": head_ms,
+                               "frac_resident": achieved / HBM_PEAK_GBPS, "achieved_resident": achieved, "kernel_ms_resident": kern_ms,
+                               "kernel_ms_from": f"HIP event pairs on every launch of a second loop of {kpasses} passes behind the timed region "
+                                                 f"({len(kern_samples)} launches; that loop's own wall time: {ms_per_step_bracketed:.4f} ms per pass)",
+                               "algorithmic_bytes_per_launch": alg_bytes, "frac_of_measured_copy_peak": head_achieved / HBM_COPY_GBPS,
+                               # what a plain copy with this sweep's access pattern reaches on this chip (tools/micro/rows_copy.hip, profiles/r04/
+                               # rows_copy_access_pattern.log: 4096 row streams 40 KB apart, one wavefront each): the layout's own ceiling
+                               "access_pattern_copy_ceiling_GBps": ({"resident": 6900.0, "cold": 5940.0} if tiled else {"resident": 6820.0, "cold": 5250.0}),
+                               "access_pattern_copy_ceiling_source": "profiles/r04/rows_copy_access_pattern.log (one wavefront per latent, 4 KB per step, this layout)",
+                               "other_layout": other_layout,
+                               # the other wall (mode F is 2 d^2 + 2 d flop per step; the d = 12 fp64 configuration sits on this one)
+                               "vector_alu": valu_side(bank.d, dtype, L * min(slab, T) / (kern_ms * 1e-3))}
+            out["ms_per_step_with_event_pairs"] = ms_per_step_bracketed
+            if stub:
+                    out["roofline"]["frac"] = None; out["roofline"]["achieved"] = None
+            for k_, v_ in cold.items():
+                out["roofline"].setdefault(k_, v_)
+            if c4_multi is not None:
+                out["other_configs"] = {"c4": c4_multi}
+            if world == 1 and not args.no_cpu and not stub:
+                if not args.no_others and not force_dist:
+                    # the other single-GPU rows of BASELINE.json / SURVEY 8, measured in the same run: the other filter shapes (kernel-exact
+                    # events + wall clock + cold leg), the gradient sweeps (mode G) and configs[2]'s objective evaluation
+                    others = {}
+                    for name in sorted(CONFIGS):
+                        if name == args.config or name in SLAB:
+                            continue
+                        others[name] = filter_row(name, device)
+                    for name in ("c3grad", "c5grad"):
+                        g = grad_row(name, 10, 2, cpu=False)
+                        others[name] = {"workload": g["config"]["workload"], "state_dim": g["config"]["state_dim"], "dtype": g["dtype"], "ms_per_step": g["ms_per_step"],
+                                        "value": g["value"], "kernel": g["roofline"]["kernel"], "kernel_ms": g["roofline"]["kernel_ms"],
+                                        "kernel_ms_from": g["roofline"]["kernel_ms_from"], "bound": "valu", "achieved_TFLOPs": g["roofline"]["achieved"],
+                                        "peak_TFLOPs": g["roofline"]["peak"], "frac": g["roofline"]["frac"], "flops_per_step": g["roofline"]["flops_per_step"],
+                                        "flop_count": g["roofline"]["flop_count"]}
+                    for nm, dt_ in (("c3e2e", torch.float32), ("c3e2e_f64", torch.float64)):
+                        try:
+                            others[nm] = e2e_row(device, dt_)
+                        except Exception as e:         # (context rows: never let one take the headline down)
+                            others[nm] = {"error": str(e)}
+                    try:
+                        others["c4"] = slab_row(device)
+                    except Exception as e:
+                        others["c4"] = {"error": str(e)}
+                    try:
+                        others["c5gaps"] = gaps_row(device)            # configs[4]'s shape with 1 % of the ticks missing, fp64 and fp32
+                    except Exception as e:
+                        others["c5gaps"] = {"error": str(e)}
+                    try:
+                        lr = learn_row(3, 1, cpu=False, windows=(128,))
+                        others["c3learn"] = {"workload": lr["config"]["workload"], "dtype": "f64", "ms_per_step": lr["ms_per_step"], "value": lr["value"],
+                                             "bound": "mfma", "achieved_TFLOPs": lr["roofline"]["achieved"], "peak_TFLOPs": 78.6, "frac": lr["roofline"]["frac"],
+                                             "update_ms": lr["roofline"]["update_ms"], "window_eval_ms": lr["roofline"]["window_eval_ms"],
+                                             "host_path_evaluation_ms": lr["roofline"]["host_path_evaluation_ms"], "note": lr["roofline"]["note"]}
+                    except Exception as e:             # (a context line: never let it take the headline down)
+                        others["c3learn"] = {"error": str(e)}
+                    try:
+                        lo = loop_row(ticks=3, threading=True)
+                        others["c3loop"] = {"workload": lo["config"]["workload"], "dtype": "f64", "ms_per_step": lo["ms_per_step"], "value": lo["value"],
+                                            "objective_evaluations_per_tick": lo["learner"]["objective_evaluations_per_tick"],
+                                            "lbfgs_iterations_per_tick": lo["learner"]["lbfgs_iterations_per_tick"],
+                                            "ms_per_objective_evaluation_incl_optimiser": lo["ms_per_objective_evaluation_incl_optimiser"]}
+                    except Exception as e:
+                        others["c3loop"] = {"error": str(e)}
+                    out["other_configs"] = others
+                if tiled:                                   # the parity leg reads series-major means
+                    if nslab > 1:
+                        yhat_slabs = [untile_stream(yt_slabs[k], Ty_slabs[k].shape[1]) for k in range(nslab)]
+                    else:
+                        yhat = untile_stream(yt, T)
                 if nslab > 1:
-                    yhat_slabs = [untile_stream(yt_slabs[k], Ty_slabs[k].shape[1]) for k in range(nslab)]
-                else:
-                    yhat = untile_stream(yt, T)
-            if nslab > 1:
-                yhat = torch.cat([y[:, :Ty_slabs[k].shape[1]] for k, y in enumerate(yhat_slabs)], dim=1)
-            sub = np.arange(0, L, max(1, L // 64))[:64]
-            cb, nll_rel, mean_rel = cpu_baseline(prm, Ty[:, :T].cpu().numpy(), T, float(total.item()), yhat[sub][:, :T].double().cpu().numpy(), sub, kernel)
-            out["cpu_baseline"] = cb
-            out["nll_rel_err"] = nll_rel
-            out["filtered_mean_rel_err"] = mean_rel
-            out["speedup_vs_cpu_all_cores"] = value / cb["value"]
+                    yhat = torch.cat([y[:, :Ty_slabs[k].shape[1]] for k, y in enumerate(yhat_slabs)], dim=1)
+                sub = np.arange(0, L, max(1, L // 64))[:64]
+                cb, nll_rel, mean_rel = cpu_baseline(prm, Ty[:, :T].cpu().numpy(), T, float(total.item()), yhat[sub][:, :T].double().cpu().numpy(), sub, kernel)
+                out["cpu_baseline"] = cb
+                out["nll_rel_err"] = nll_rel
+                out["filtered_mean_rel_err"] = mean_rel
+                out["speedup_vs_cpu_all_cores"] = value / cb["value"]
         print(json.dumps(out), flush=True)
     if multi:
         dist.destroy_process_group()

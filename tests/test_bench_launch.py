@@ -33,8 +33,10 @@ def test_bench_starts_its_own_ranks(n):
 
 
 def test_bench_reports_a_failing_rank():
-    # a config the stub ranks cannot run (it needs the GPU objects): the children fail, the parent must not exit 0 or print a line
-    r = _run({"BENCH_REHEARSAL": "stub"}, "--gpus", "2", "--steps", "2", "--warmup", "0", "--config", "c3grad", timeout=300)
+    # ranks that fail after their process group is up (c3loop refuses --dump-outputs, with or without a GPU on the box): the children
+    # fail, the parent must not exit 0 or print a line
+    r = _run({"BENCH_REHEARSAL": "stub"}, "--gpus", "2", "--steps", "2", "--warmup", "0", "--config", "c3loop", "--dump-outputs", "unused",
+             timeout=300)
     assert r.returncode != 0
     assert not [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
 
@@ -42,3 +44,22 @@ def test_bench_reports_a_failing_rank():
 def test_bench_refuses_a_world_size_mismatch():
     r = _run({"BENCH_REHEARSAL": "stub", "WORLD_SIZE": "1", "RANK": "0"}, "--gpus", "2", "--steps", "1")
     assert r.returncode != 0 and "WORLD_SIZE" in (r.stderr + r.stdout)
+
+
+def test_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    # a plain run carries the headline only and writes the last timed step's outputs; --full adds the figures that take runs of their own
+    import numpy as np
+    r = _run({"BENCH_REHEARSAL": "stub"}, "--gpus", "1", "--steps", "7", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")][-1])
+    assert out["steps"] == 7 and out["ms_per_step"] > 0 and out["unit"] == "Kalman steps/s" and out["higher_is_better"] is True
+    assert "roofline" not in out and "cpu_baseline" not in out and "other_configs" not in out
+    files = sorted(p.name for p in tmp_path.iterdir())
+    assert files == ["nll.npy", "nll_total.npy", "x.npy", "yhat.npy"], files
+    arrays = [np.load(tmp_path / f) for f in files]
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays)
+    assert sum(os.path.getsize(tmp_path / f) for f in files) <= 64 * 10 ** 6
+    r = _run({"BENCH_REHEARSAL": "stub"}, "--gpus", "1", "--steps", "2", "--warmup", "0", "--full")
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")][-1])
+    assert out["steps"] == 2 and "roofline" in out and "ms_per_step_with_event_pairs" in out

@@ -7,9 +7,9 @@ O=gpurun_out/j10
 echo "== tests" | tee $O/progress.log
 timeout -k 10 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_configs.py -x -q -k "many_latent or segment_major or bench or full_size_properties" > $O/tests.log 2>&1; echo "tests rc=$?" | tee -a $O/progress.log; tail -4 $O/tests.log
 echo "== bench c3 resident / rotate (no others)" | tee -a $O/progress.log
-timeout -k 10 300 python bench.py --no-others --no-cpu --no-cold --steps 100 > $O/b_res.json 2> $O/b_res.err; echo "rc=$?" >> $O/progress.log
-timeout -k 10 300 python bench.py --no-others --no-cpu --no-cold --steps 100 --rotate > $O/b_rot.json 2> $O/b_rot.err; echo "rc=$?" >> $O/progress.log
-timeout -k 10 300 python bench.py --no-others --no-cpu > $O/b_def.json 2> $O/b_def.err; echo "rc=$?" >> $O/progress.log
+timeout -k 10 300 python bench.py --full --no-others --no-cpu --no-cold --steps 100 > $O/b_res.json 2> $O/b_res.err; echo "rc=$?" >> $O/progress.log
+timeout -k 10 300 python bench.py --full --no-others --no-cpu --no-cold --steps 100 --rotate > $O/b_rot.json 2> $O/b_rot.err; echo "rc=$?" >> $O/progress.log
+timeout -k 10 300 python bench.py --full --no-others --no-cpu > $O/b_def.json 2> $O/b_def.err; echo "rc=$?" >> $O/progress.log
 python - <<'PY'
 import json
 for n in ("b_res","b_rot","b_def"):

@@ -15,7 +15,7 @@ echo "loop prof rc=$?" | tee -a $O/progress.log
 f=$(find $O/prof_loop -name "*kernel_stats.csv" | head -1); head -30 "$f" | cut -c1-200 > $O/loop_kernel_stats_top.csv; cat $O/loop_kernel_stats_top.csv | cut -c1-160
 rm -rf $O/prof_loop
 echo "== bench default" | tee -a $O/progress.log
-timeout -k 10 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?" | tee -a $O/progress.log
+timeout -k 10 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc=$?" | tee -a $O/progress.log
 python - <<'PY'
 import json
 d=json.load(open("gpurun_out/j4/bench_default.json"))

@@ -7,14 +7,14 @@ out=$1; tag=$2
 cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 mkdir -p "$out"
-python3 bench.py > "$out/${tag}_default_bench_all_rows.json" 2> "$out/${tag}_default_bench.err"; echo "bench default done"
+python3 bench.py --full > "$out/${tag}_default_bench_all_rows.json" 2> "$out/${tag}_default_bench.err"; echo "bench default done"
 for c in c4 c1 c3grad c5grad c3learn c3loop; do
-  python3 bench.py --config $c > "$out/${tag}_${c}_bench.json" 2> "$out/${tag}_${c}_bench.err" || echo "bench $c FAILED"
+  python3 bench.py --full --config $c > "$out/${tag}_${c}_bench.json" 2> "$out/${tag}_${c}_bench.err" || echo "bench $c FAILED"
   echo "bench $c done"
 done
-python3 bench.py --layout series --no-others > "$out/${tag}_c3_series_major_bench.json" 2> "$out/${tag}_c3_series.err"; echo "bench c3 series done"
+python3 bench.py --full --layout series --no-others > "$out/${tag}_c3_series_major_bench.json" 2> "$out/${tag}_c3_series.err"; echo "bench c3 series done"
 prof() {   # name, config, extra flags
-  rocprofv3 --kernel-trace --stats --output-format csv -d "$out/prof_$1/kt" -o out -- python3 bench.py --config $2 --steps 200 --warmup 150 --no-cpu --no-cold --no-others $3 > "$out/${tag}_$1_bench_under_rocprof.json" 2> "$out/prof_$1.err"
+  rocprofv3 --kernel-trace --stats --output-format csv -d "$out/prof_$1/kt" -o out -- python3 bench.py --full --config $2 --steps 200 --warmup 150 --no-cpu --no-cold --no-others $3 > "$out/${tag}_$1_bench_under_rocprof.json" 2> "$out/prof_$1.err"
   python3 profiles/summarize.py "$out/prof_$1" "$out" "${tag}_$1" filter_ > /dev/null
   rm -rf "$out/prof_$1"
   echo "rocprof $1 done"
