@@ -236,6 +236,38 @@ int moihgp_filter_stream_tiled(moihgp_gp* gp, int dtype, const void* Ty_tiled, s
                                double* nll_total, void* stream);
 int moihgp_stream_retile(int dtype, const void* src, void* dst, size_t L, size_t T, size_t ld, int to_tiled, void* stream);
 
+/* ---- steady-state RTS smoothing of whole streams (not in the reference; its IHGP::backwardSmoother, ihgp.h:103-114, is dead code) ----------
+ * The posterior of every latent at every tick given ALL the ticks of the stream, where moihgp_filter_stream* gives the filtered means (ticks
+ * up to their own).  A separate estimator of the same model: the learners' filter, NLL and gradients keep the reference's literal gains.
+ * Per latent, from the handle's hyper-parameters: A = expm(dt F) (the handle's A), Q = sym(Pinf - A Pinf A^T), H = e0, R = the noise parameter,
+ *     P   solves  P = A P A^T - A P H^T (H P H^T + R)^-1 H P A^T + Q     (the Kalman form, by structure-preserving doubling and two Newton
+ *                                                                        steps, relative residual <= 1e-12 or status 1; NOT the un-transposed
+ *                                                                        DARE of ihgp.h:125, whose gain below diverges)
+ *     S = H P H^T + R,  K = P H^T / S,  PF = P - K H P,  G = PF A^T P^-1
+ *     Ps  solves  Ps = G Ps G^T + PF - G P G^T                           (exact d^2 x d^2 linear solve)
+ *     var_filtered = H PF H^T,  var_smoothed = H Ps H^T
+ * and, with x_in the state before tick 0:
+ *     forward:   xp[t] = A xf[t-1] (xf[-1] = x_in);  p[t] = H xp[t];  v[t] = y[t] - p[t] (0 where y[t] is NaN);  xf[t] = xp[t] + K v[t]
+ *     backward:  s[T] = 0;  s[t] = G s[t+1] + K v[t];  ysmooth[t] = p[t] + s[t]_0
+ * (the RTS form xs[t] = xf[t] + G (xs[t+1] - A xf[t]); xs[T-1] = xf[T-1]).  The gains are the steady-state ones: in the interior of a long
+ * gap-free stream the result is the exact GP posterior mean (and var_smoothed its variance); within a few correlation lengths of the two ends
+ * and of missing ticks it is the IHGP approximation, not the exact posterior.
+ * moihgp_smooth_stream: Ty [L][ld_in] series-major (dtype), ysmooth [L][ld_out] (dtype; must not overlap Ty), same stride and alignment rules as
+ *   moihgp_filter_stream_v2.  The forward sweep writes the predicted means into ysmooth and the backward sweep smooths them in place.
+ *   x_in [L][d] state before tick 0; x [L][d] end state (filtered = smoothed at T-1; may alias x_in).  status: DEVICE int [L] or NULL
+ *   (0 ok, 1 Kalman DARE not converged: that latent's row and end state are NaN).  No NLL: the learners' objective stays moihgp_filter_stream*'s.
+ *   Asynchronous on `stream`, which joins the handle's set of streams that carry batched work.  The smoother's tables are built on the first
+ *   smooth after a table rewrite (gpXX_update, moihgp_update_latents, ...), on that call's stream: the rewrites themselves do no extra work.
+ *   Option "smoother_path" (moihgp_set_option): -1 automatic (the time-parallel scan kernels, a serial fp64 walk for latents whose G or A - K H A
+ *   fails a growth bound), 0 scan kernels for every latent, 1 serial fp64 walk for every latent.  Stacked models: 3.
+ * moihgp_get_smoother: latent l's P [d*d], K [d], G [d*d], Ps [d*d] (row-major), var_filtered, var_smoothed, to HOST buffers (any may be NULL).
+ * moihgp_latent_variances: var_filtered [L], var_smoothed [L] to HOST buffers (either may be NULL).  Both synchronise. */
+int moihgp_smooth_stream(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x,
+                         void* ysmooth, size_t ld_out, int* status, void* stream);
+int moihgp_get_smoother(moihgp_gp* gp, size_t l, double* P, double* K, double* G, double* Ps,
+                        double* var_filtered, double* var_smoothed);
+int moihgp_latent_variances(moihgp_gp* gp, double* var_filtered, double* var_smoothed);
+
 /* As above plus the hyper-parameter sensitivities (ihgp.h:54) and the per-latent NLL gradient
  * (ihgp.h:216-220), summed over ticks:
  *   dx   [L][P][d] in/out (dtype);  grad [L][P] doubles out. */

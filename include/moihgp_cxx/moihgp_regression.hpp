@@ -8,6 +8,7 @@
 #ifndef MOIHGP_CXX_MOIHGP_REGRESSION_HPP_
 #define MOIHGP_CXX_MOIHGP_REGRESSION_HPP_
 
+#include <cstring>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -109,6 +110,44 @@ public:
             x = xnew;
         }
         return Yhat;
+    }
+    // (not in the reference) The steady-state RTS smoother of the whole series with the current parameters (include/moihgp.h
+    // moihgp_smooth_stream): the posterior mean of every output at every tick given ALL of Y, from a zero start state, where predict()
+    // returns filtered means.  fp64 on the device: project_stream -> smooth_stream -> unproject_stream.  Throws std::runtime_error if a latent's
+    // Kalman DARE did not converge (status 1: its row would be NaN).  Missing outputs (NaN) go through moihgp_project_stream's least-squares
+    // projection, which has limits predict() does not: a tick with more than 64 missing outputs, or fewer than num_latent observed ones, is
+    // treated as missing as a whole (the smoother then carries the state across it).
+    std::vector<Vector> predictSmoothed(const std::vector<Vector>& Y) {
+        const size_t T = Y.size(), M = _num_output, L = _num_latent, ld = (T + 1) / 2 * 2;
+        std::vector<Vector> Ys(T, Vector(M, 0.0));
+        if (T == 0) return Ys;
+        Vector flat(T * M), zeros(L * _dim, 0.0);
+        for (size_t t = 0; t < T; t++) for (size_t m = 0; m < M; m++) flat[t * M + m] = Y[t][m];
+        moihgp_dvec_ctx* ctx = moihgp_dvec_ctx_new();
+        const size_t nst = (L + 1) / 2;                             // status words: L ints in doubles' storage
+        double *dY = moihgp_dvec_alloc(T * M), *dTy = moihgp_dvec_alloc(L * ld), *dys = moihgp_dvec_alloc(L * ld), *dx = moihgp_dvec_alloc(L * _dim),
+               *dst = moihgp_dvec_alloc(nst);
+        int rc = (ctx && dY && dTy && dys && dx && dst) ? 0 : 4;
+        Vector st(nst, 0.0);
+        void* s = ctx ? moihgp_dvec_ctx_stream(ctx) : nullptr;
+        moihgp_gp* h = _moihgp->handle();
+        if (!rc) rc = moihgp_dvec_upload(ctx, dY, flat.data(), T * M);
+        if (!rc) rc = moihgp_dvec_upload(ctx, dx, zeros.data(), L * _dim);
+        if (!rc) rc = moihgp_project_stream(h, MOIHGP_F64, dY, T, dTy, ld, s);
+        if (!rc) rc = moihgp_smooth_stream(h, MOIHGP_F64, dTy, T, ld, dx, dx, dys, ld, reinterpret_cast<int*>(dst), s);
+        if (!rc) rc = moihgp_unproject_stream(h, MOIHGP_F64, dys, T, ld, dY, s);
+        if (!rc) rc = moihgp_dvec_download(ctx, flat.data(), dY, T * M);
+        if (!rc) rc = moihgp_dvec_download(ctx, st.data(), dst, nst);
+        if (ctx) { moihgp_dvec_sync(ctx); moihgp_release_stream(h, s); }
+        for (double* p : {dY, dTy, dys, dx, dst}) if (p) moihgp_dvec_free(p);
+        if (ctx) moihgp_dvec_ctx_del(ctx);
+        if (rc) throw std::runtime_error(std::string("predictSmoothed: ") + moihgp_last_error());
+        std::vector<int> status(2 * nst, 0);
+        std::memcpy(status.data(), st.data(), sizeof(double) * nst);
+        for (size_t l = 0; l < L; l++)
+            if (status[l] != 0) throw std::runtime_error("predictSmoothed: the Kalman DARE of latent " + std::to_string(l) + " did not converge");
+        for (size_t t = 0; t < T; t++) for (size_t m = 0; m < M; m++) Ys[t][m] = flat[t * M + m];
+        return Ys;
     }
     Vector getParams() { return _moihgp->getParams(); }
     size_t getNumParam() { return _num_param; }

@@ -123,13 +123,19 @@ struct moihgp_gp {
     unsigned prof_stride = 1, prof_seen = 0;     // every prof_stride-th launch carries an event pair (moihgp_profile_stride)
     std::vector<hipEvent_t> prof_ev;
     int prof_n = 0;
+    // steady-state RTS smoother (moihgp_smooth_stream): its per-latent tables, built lazily on the first smooth after a table rewrite
+    double* dsm = nullptr;
+    bool sm_stale = true;
+    hipStream_t sm_built_on = nullptr;   // stream that carried the last build; sm_ev marks its end for the other streams / host reads
+    hipEvent_t sm_ev = nullptr;
+    int opt_smoother_path = -1;          // option "smoother_path": -1 automatic, 0 scan kernels, 1 serial fp64
 
     TickArgs tick() const { return TickArgs{d, M, L, cb64, dU, dS, dsqrtS, dinvsqrtS, dsigma, (threading || lik1_full) ? 1 : 0, P, cbd64}; }
 };
 
 static void gp_free(moihgp_gp* g) {
     if (!g) return;
-    void* ptrs[] = {g->dU, g->dS, g->dsqrtS, g->dinvsqrtS, g->dsigma, g->dparams, g->cb64, g->cb32, g->dx, g->dpart, g->dTy, g->dUty, g->dTyhat, g->dloss, g->dgrad, g->dscratch, g->dwork, g->dpolar, g->dfallback, g->dwin, g->dunstable, g->dxscratch, g->cbd64, g->dU32, g->dhp, g->dlink, g->dwinmiss, g->dtp64, g->dtp32, g->dxc64, g->dxc32, g->dlinkflags, g->dgap, g->drescue_idx, g->drescue, g->drescue_const};
+    void* ptrs[] = {g->dU, g->dS, g->dsqrtS, g->dinvsqrtS, g->dsigma, g->dparams, g->cb64, g->cb32, g->dx, g->dpart, g->dTy, g->dUty, g->dTyhat, g->dloss, g->dgrad, g->dscratch, g->dwork, g->dpolar, g->dfallback, g->dwin, g->dunstable, g->dxscratch, g->cbd64, g->dU32, g->dhp, g->dlink, g->dwinmiss, g->dtp64, g->dtp32, g->dxc64, g->dxc32, g->dlinkflags, g->dgap, g->drescue_idx, g->drescue, g->drescue_const, g->dsm};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (void* p : g->pinned) (void)hipHostUnregister(p);
@@ -139,6 +145,7 @@ static void gp_free(moihgp_gp* g) {
     if (g->hflag) (void)hipHostFree(g->hflag);
     for (hipEvent_t e : g->prof_ev) (void)hipEventDestroy(e);
     if (g->order_ev) (void)hipEventDestroy(g->order_ev);
+    if (g->sm_ev) (void)hipEventDestroy(g->sm_ev);
     if (g->stream) (void)hipStreamDestroy(g->stream);
     delete g;
 }
@@ -196,6 +203,7 @@ static void upload_mixing(moihgp_gp* g) {
 static void run_ihgp_update(moihgp_gp* g) {
     order_after_sweeps(g);
     g->hp_valid = false;
+    g->sm_stale = true;                 // the smoother's tables follow on the next smooth (nothing is computed for them here)
     g->cb_version++;
     MOIHGP_HIP_FATAL(hipMemcpyAsync(g->dparams, g->igp.data(), sizeof(double) * g->L * g->P, hipMemcpyHostToDevice, g->stream));
     if (kernel_stack(g->kernel)) {
@@ -918,6 +926,95 @@ int moihgp_filter_stream_tiled(moihgp_gp* gp, int dtype, const void* Ty, size_t 
     return guard_rc([&] { return filter_stream_tiled_impl(gp, dtype, Ty, T, x_in, x, yhat, nll, nll_total, stream); });
 }
 
+// ---- steady-state RTS smoother (smoother.hip) ----------------------------------------------------------------------------------------------
+// Its tables are built on the first smooth after a table rewrite, on that call's stream; sm_ev marks the end of the build, and a smooth on
+// another stream (or a host read) waits for it.  A rewrite (run_ihgp_update) waits for every stream that carried batched work and
+// synchronises, so no smooth still reads the old tables when the next build overwrites them.
+static int ensure_smoother(moihgp_gp* g, hipStream_t s) {
+    if (kernel_stack(g->kernel)) { set_last_error("smoother: stacked models are not supported (Matern-3/2 and -5/2 only)"); return 3; }
+    if (!g->dsm) g->dsm = dev_alloc<double>(g->L * (size_t)sm_size(g->d));
+    if (!g->sm_ev) MOIHGP_HIP_FATAL(hipEventCreateWithFlags(&g->sm_ev, hipEventDisableTiming));
+    if (g->sm_stale) {
+        launch_smoother_tables(kernel_base(g->kernel), g->d, g->cb64, g->L, g->dsm, s);
+        MOIHGP_HIP_FATAL(hipEventRecord(g->sm_ev, s));
+        g->sm_built_on = s;
+        g->sm_stale = false;
+    } else if (s != g->sm_built_on) {
+        MOIHGP_HIP_FATAL(hipStreamWaitEvent(s, g->sm_ev, 0));
+    }
+    return 0;
+}
+
+static int smooth_stream_impl(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x, void* ys, size_t ld_out,
+                              int* status, void* stream) {
+    if (int rc = check_stream_args(gp, dtype, Ty, T, ld_in, x)) return rc;
+    if (!x_in) { set_last_error("null start state"); return 1; }
+    const size_t es = dtype == MOIHGP_F64 ? 8 : 4, epv = 16 / es;
+    if (!ys && T > 0) { set_last_error("null ysmooth"); return 1; }
+    if (ys && ((uintptr_t)ys & 15) != 0) { set_last_error("ysmooth base must be 16-byte aligned"); return 1; }
+    if (ys && (ld_out % epv != 0 || ld_out < (T + epv - 1) / epv * epv)) {
+        set_last_error("ld_out (%zu) must be a multiple of %zu and >= T rounded up to it", ld_out, epv);
+        return 1;
+    }
+    if (ys && T > 0) {   // the backward sweep reads y after the forward one wrote the predicted means: the two may not overlap
+        const uintptr_t a0 = (uintptr_t)Ty, a1 = a0 + gp->L * ld_in * es, b0 = (uintptr_t)ys, b1 = b0 + gp->L * ld_out * es;
+        if (a0 < b1 && b0 < a1) { set_last_error("ysmooth must not overlap the input stream"); return 1; }
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = ensure_smoother(gp, s)) return rc;
+    note_user_stream(gp, s);
+    launch_smooth_stream(gp->d, dtype, Ty, T, ld_in, gp->L, gp->dsm, x_in, x, ys, ld_out, status, gp->opt_smoother_path, s);
+    return 0;
+}
+
+// host copy of the smoother blocks of latents [l0, l0 + n), built first if stale (on the handle's stream)
+static int read_smoother(moihgp_gp* gp, size_t l0, size_t n, std::vector<double>& out) {
+    if (int rc = ensure_smoother(gp, gp->stream)) return rc;
+    MOIHGP_HIP_FATAL(hipEventSynchronize(gp->sm_ev));
+    const size_t bs = (size_t)sm_size(gp->d);
+    out.resize(n * bs);
+    MOIHGP_HIP_FATAL(hipMemcpyAsync(out.data(), gp->dsm + l0 * bs, sizeof(double) * n * bs, hipMemcpyDeviceToHost, gp->stream));
+    MOIHGP_HIP_FATAL(hipStreamSynchronize(gp->stream));
+    return 0;
+}
+
+static int get_smoother_impl(moihgp_gp* gp, size_t l, double* P, double* K, double* G, double* Ps, double* var_f, double* var_s) {
+    if (!gp || l >= gp->L) { set_last_error("get_smoother: bad latent index"); return 1; }
+    std::vector<double> b;
+    if (int rc = read_smoother(gp, l, 1, b)) return rc;
+    int off[14];
+    sm_offsets(gp->d, off);
+    const int d = gp->d, nn = d * d;
+    auto cp = [&](double* dst, int o, int n) { if (dst) std::memcpy(dst, b.data() + o, sizeof(double) * n); };
+    cp(P, off[6], nn); cp(K, off[2], d); cp(G, off[3], nn); cp(Ps, off[8], nn); cp(var_f, off[9], 1); cp(var_s, off[10], 1);
+    return 0;
+}
+
+static int latent_variances_impl(moihgp_gp* gp, double* var_f, double* var_s) {
+    if (!gp) { set_last_error("null handle"); return 1; }
+    std::vector<double> b;
+    if (int rc = read_smoother(gp, 0, gp->L, b)) return rc;
+    int off[14];
+    sm_offsets(gp->d, off);
+    const size_t bs = (size_t)sm_size(gp->d);
+    for (size_t l = 0; l < gp->L; l++) {
+        if (var_f) var_f[l] = b[l * bs + off[9]];
+        if (var_s) var_s[l] = b[l * bs + off[10]];
+    }
+    return 0;
+}
+
+int moihgp_smooth_stream(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x, void* ysmooth, size_t ld_out,
+                         int* status, void* stream) {
+    return guard_rc([&] { return smooth_stream_impl(gp, dtype, Ty, T, ld_in, x_in, x, ysmooth, ld_out, status, stream); });
+}
+int moihgp_get_smoother(moihgp_gp* gp, size_t l, double* P, double* K, double* G, double* Ps, double* var_filtered, double* var_smoothed) {
+    return guard_rc([&] { return get_smoother_impl(gp, l, P, K, G, Ps, var_filtered, var_smoothed); });
+}
+int moihgp_latent_variances(moihgp_gp* gp, double* var_filtered, double* var_smoothed) {
+    return guard_rc([&] { return latent_variances_impl(gp, var_filtered, var_smoothed); });
+}
+
 int moihgp_stream_retile(int dtype, const void* src, void* dst, size_t L, size_t T, size_t ld, int to_tiled, void* stream) {
     return guard_rc([&] {
         if (dtype != MOIHGP_F64 && dtype != MOIHGP_F32) { set_last_error("dtype must be MOIHGP_F64 or MOIHGP_F32"); return 1; }
@@ -1221,6 +1318,7 @@ int moihgp_set_option(moihgp_gp* gp, const char* name, long value) {
     if (n == "filter_plain_x") { if (value < -1 || value > 1) { set_last_error("filter_plain_x: -1 (automatic), 0 (never), 1 (always: the stacked filter's kernels for Matern-3/2 and -5/2)"); return 1; } gp->opt_filter_plain_x = (int)value; return 0; }
     if (n == "filter_team") { if (value < -1 || value > 2) { set_last_error("filter_team: -1 (automatic), 0 (never), 1 (whenever the stream fits), 2 (the 32-tick-chunk form only)"); return 1; } gp->opt_filter_team = (int)value; return 0; }
     if (n == "filter_maxlinks") { if (value < -1 || value > 64) { set_last_error("filter_maxlinks: -1 (automatic) .. 64"); return 1; } gp->opt_filter_maxlinks = (int)value; return 0; }
+    if (n == "smoother_path") { if (value < -1 || value > 1) { set_last_error("smoother_path: -1 (automatic), 0 (scan kernels), 1 (serial fp64)"); return 1; } gp->opt_smoother_path = (int)value; return 0; }
     if (n == "filter_variant") {
 #ifdef MOIHGP_TUNING
         gp->opt_filter_variant = (int)value; return 0;

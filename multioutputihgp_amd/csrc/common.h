@@ -193,6 +193,14 @@ int launch_gap_impulse(const GapBank& b, int kernel, int dtype, size_t L, const 
 // recursion.hip: the same sweep over segment-major streams [ceil(T / SEG)][L][SEG], SEG = 4096 / sizeof(scalar) ticks (d = 2, 3)
 int launch_filter_stream_tiled(int d, int dtype, const void* Ty, size_t T, size_t L, const double* cb64, const float* cb32, const void* xin, void* x,
                                void* yhat, double* nll, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, int n_unstable, double* total, int variant = 0);
+// smoother.hip: steady-state RTS smoothing (include/moihgp.h moihgp_smooth_stream).  Per-latent fp64 block of sm_size(d) doubles;
+// sm_offsets fills 14 offsets: A AKHA K G MF MB P PF PS VARF VARS GROWTH RESID STATUS.
+int sm_size(int d);
+void sm_offsets(int d, int* off);
+void launch_smoother_tables(int kernel, int d, const double* cb64, size_t L, double* tabs, hipStream_t stream);
+// path: -1 automatic (scan kernels for the latents that pass the growth bound), 0 scan kernels, 1 serial fp64 for every latent
+void launch_smooth_stream(int d, int dtype, const void* Ty, size_t T, size_t ld_in, size_t L, const double* tabs, const void* x_in, void* x,
+                          void* ys, size_t ld_out, int* status, int path, hipStream_t stream);
 // series-major [L][ld] <-> segment-major [ceil(T / SEG)][L][SEG] (to_tiled != 0: src is series-major; ticks past T are written as zeros)
 int launch_stream_retile(int dtype, const void* src, void* dst, size_t L, size_t T, size_t ld, int to_tiled, hipStream_t stream);
 // recursion.hip: batched sweeps over series-major streams.

@@ -42,6 +42,53 @@ __device__ inline bool all_zero(const double* A) {
     return true;
 }
 
+template <int D>
+struct SS {
+    double F[D * D], Pinf[D * D], H[D], R;
+    double dF[3][D * D], dPinf[3][D * D], dR[3];
+};
+
+// matern32ss.h:40-64 (D == 2) and matern52ss.h:38-75 (D == 3), including `lam = sqrt(3)/l` there.
+template <int D>
+__device__ void ss_build(int kernel, const double* params, SS<D>& s) {
+    for (int i = 0; i < D * D; i++) {
+        s.F[i] = 0.0; s.Pinf[i] = 0.0;
+        for (int p = 0; p < 3; p++) { s.dF[p][i] = 0.0; s.dPinf[p][i] = 0.0; }
+    }
+    for (int i = 0; i < D; i++) s.H[i] = 0.0;
+    s.H[0] = 1.0;
+    double magnitude = params[0], lengthscale = params[1];
+    s.R = params[2];
+    s.dR[0] = 0.0; s.dR[1] = 0.0; s.dR[2] = 1.0;
+    if constexpr (D == 2) {
+        double lam = sqrt(3.0) / lengthscale, lam2 = lam * lam;
+        double len3 = 6.0 / (lengthscale * lengthscale * lengthscale);
+        s.F[1] = 1.0;
+        s.F[2] = -lam2;
+        s.F[3] = -2.0 * lam;
+        s.Pinf[0] = magnitude;
+        s.Pinf[3] = magnitude * lam2;
+        s.dF[1][2] = len3;
+        s.dF[1][3] = 2.0 * lam / lengthscale;
+        s.dPinf[0][0] = 1.0;
+        s.dPinf[0][3] = lam2;
+        s.dPinf[1][3] = -magnitude * len3;
+    } else {
+        double lam = sqrt(3.0) / lengthscale;
+        double lam2 = lam * lam, len2 = lengthscale * lengthscale, len3 = len2 * lengthscale, len4 = len2 * len2;
+        double kappa = 5.0 / 3.0 * magnitude / len2, kappa2 = -2.0 * kappa / lengthscale, sq5 = sqrt(5.0);
+        s.F[1] = 1.0; s.F[5] = 1.0;
+        s.F[6] = -lam2 * lam; s.F[7] = -3.0 * lam2; s.F[8] = -3.0 * lam;
+        s.Pinf[0] = magnitude; s.Pinf[8] = 25.0 * magnitude / len4; s.Pinf[4] = kappa;
+        s.Pinf[6] = -kappa; s.Pinf[2] = -kappa;
+        s.dF[1][6] = 15.0 * sq5 / len4; s.dF[1][7] = 30.0 / len3; s.dF[1][8] = sq5 * lam2;
+        for (int i = 0; i < 9; i++) s.dPinf[0][i] = s.Pinf[i] / magnitude;
+        s.dPinf[1][4] = kappa2; s.dPinf[1][6] = -kappa2; s.dPinf[1][2] = -kappa2;
+        s.dPinf[1][8] = -100.0 * magnitude / len2 / len3;
+    }
+    (void)kernel;
+}
+
 // X = Den^-1 Num, partial pivoting (Eigen partialPivLu().solve)
 template <int N>
 __device__ void lu_solve(const double* Ain, const double* Bin, double* X) {

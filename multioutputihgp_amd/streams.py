@@ -263,6 +263,53 @@ class LatentBank:
         _check(rc, self._lib)
         return dict(yhat=yhat, x=x, dx=dx, nll=nll, grad=grad)
 
+    def smooth(self, Ty: torch.Tensor, T: Optional[int] = None, x: Optional[torch.Tensor] = None, x_start: Optional[torch.Tensor] = None,
+               ysmooth: Optional[torch.Tensor] = None, stream=None):
+        """Steady-state RTS smoothing of T ticks for every latent (include/moihgp.h moihgp_smooth_stream): the posterior mean at every tick
+        given the whole stream, with the Kalman DARE's gains (not the learners' literal ones).
+
+        Returns (ysmooth [L, >=T], x [L, d] end state (filtered = smoothed), status [L] int32: 0 ok, 1 DARE not converged (row NaN)).
+        Asynchronous on the current torch stream.  The sweep starts from `x_start` if given, else from `x`, else from zeros; `x` receives the
+        end state in place.  `ysmooth` (optional) must not overlap Ty; its row stride may differ from the stream's."""
+        T, ld = self._check_stream(Ty, T)
+        if self.stacked:
+            raise MoihgpError("smooth: stacked models are not supported (Matern-3/2 and -5/2 only)", 3)
+        if x is None:
+            x = torch.zeros((self.L, self.d), dtype=Ty.dtype, device=Ty.device)
+        for name, t in (("x", x), ("x_start", x_start)):
+            if t is not None and (t.dtype != Ty.dtype or not t.is_contiguous() or tuple(t.shape) != (self.L, self.d)):
+                raise ValueError(f"{name} must be a contiguous [L, d] tensor of the stream dtype")
+        if ysmooth is None:
+            ysmooth = alloc_stream(self.L, max(T, 1), Ty.dtype, Ty.device)[:, :T]
+        elif (not ysmooth.is_cuda or ysmooth.dtype != Ty.dtype or ysmooth.dim() != 2 or ysmooth.stride(1) != 1 or ysmooth.shape[0] != self.L
+              or ysmooth.shape[1] < T or (self.L > 1 and ysmooth.stride(0) < padded_len(T, Ty.dtype))
+              or ysmooth.stride(0) % (2 if Ty.dtype == torch.float64 else 4) != 0):
+            raise ValueError("ysmooth must be a CUDA tensor [L, >=T] of the stream's dtype, unit stride along time, row stride a multiple of "
+                             "16 bytes and >= T rounded up to it")
+        ld_out = ysmooth.stride(0) if self.L > 1 else padded_len(max(T, 1), Ty.dtype)
+        status = torch.empty((self.L,), dtype=torch.int32, device=Ty.device)
+        rc = self._lib.moihgp_smooth_stream(self._h, _DT[Ty.dtype], C.c_void_p(Ty.data_ptr()), T, ld,
+                                            C.c_void_p((x if x_start is None else x_start).data_ptr()), C.c_void_p(x.data_ptr()),
+                                            C.c_void_p(ysmooth.data_ptr()), ld_out, C.c_void_p(status.data_ptr()), _stream_ptr(stream))
+        _check(rc, self._lib)
+        return ysmooth, x, status
+
+    def smoother(self, l: int) -> dict:
+        """The smoother's stationary quantities of latent l (moihgp_get_smoother): P (Kalman DARE), K, G, Ps, var_filtered, var_smoothed."""
+        d = self.d
+        out = dict(P=np.zeros((d, d)), K=np.zeros(d), G=np.zeros((d, d)), Ps=np.zeros((d, d)), var_filtered=np.zeros(1), var_smoothed=np.zeros(1))
+        ptrs = [out[k].ctypes.data_as(c_double_p) for k in ("P", "K", "G", "Ps", "var_filtered", "var_smoothed")]
+        _check(self._lib.moihgp_get_smoother(self._h, int(l), *ptrs), self._lib)
+        out["var_filtered"] = float(out["var_filtered"][0])
+        out["var_smoothed"] = float(out["var_smoothed"][0])
+        return out
+
+    def latent_variances(self):
+        """(var_filtered [L], var_smoothed [L]) of every latent (moihgp_latent_variances), fp64 numpy arrays."""
+        vf, vs = np.zeros(self.L), np.zeros(self.L)
+        _check(self._lib.moihgp_latent_variances(self._h, vf.ctypes.data_as(c_double_p), vs.ctypes.data_as(c_double_p)), self._lib)
+        return vf, vs
+
 
 def project_stream(gp, Y: torch.Tensor, stream=None) -> torch.Tensor:
     """OILMM projection of a tick-major observation stream Y [T, M] with the mixing of `gp`
@@ -284,3 +331,27 @@ def unproject_stream(gp, Tyhat: torch.Tensor, T: int, stream=None) -> torch.Tens
     _check(lib.moihgp_unproject_stream(gp.handle, _DT[Tyhat.dtype], C.c_void_p(Tyhat.data_ptr()), T, Tyhat.stride(0),
                                        C.c_void_p(Yhat.data_ptr()), _stream_ptr(stream)), lib)
     return Yhat
+
+
+def smooth_outputs(gp, Y: torch.Tensor, stream=None):
+    """Smoothed outputs of a tick-major observation stream Y [T, M] (NaN = missing output) with the parameters of `gp` (a pywrapper.MOIHGP):
+    project_stream -> LatentBank.smooth -> unproject_stream, from a zero state.
+
+    Returns (Ys [T, M] in Y's dtype, var_Y [M] fp64 numpy) with var_Y[m] = sum_l U[m, l]^2 S_l var_smoothed[l]: the steady-state posterior
+    variance of the latent FUNCTION at output m (interior ticks), without the observation noise.  Raises MoihgpError if any latent's Kalman DARE
+    did not converge (status 1).  Ticks with missing outputs are projected as project_stream does it: a tick with more than 64 missing outputs
+    or fewer than L observed ones is treated as missing as a whole."""
+    T = Y.shape[0]
+    bank = LatentBank.from_handle(gp)
+    Ty = project_stream(gp, Y, stream=stream)
+    ys, _, status = bank.smooth(Ty, T=T, stream=stream)
+    Ys = unproject_stream(gp, ys, T, stream=stream)
+    bad = int((status != 0).sum())      # (synchronises)
+    if bad:
+        raise MoihgpError(f"smooth_outputs: the Kalman DARE of {bad} latent(s) did not converge; their rows are NaN and so is every output "
+                          "that mixes them", 1)
+    M, L = gp.num_output, gp.num_latent
+    prm = gp.params
+    U, S = prm[:M * L].reshape(M, L), prm[M * L:M * L + L]
+    _, vs = bank.latent_variances()
+    return Ys, (U ** 2) @ (S * vs)

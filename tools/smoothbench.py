@@ -1,0 +1,61 @@
+"""Timing of the steady-state RTS smoother (moihgp_smooth_stream) at C3's shape: 4096 latents x 10^4 ticks, Matern-5/2.
+
+Prints one line per (dtype, cache state) with the event-timed duration of a whole smooth call (forward + backward + the small status kernel)
+and the algorithmic traffic of its stream passes (forward: read y, write p; backward: read y, read p, write ys).  "cold" evicts the caches
+between calls by writing a 2 GB buffer; "resident" repeats the call on the same buffers.  Run under `rocprofv3 --kernel-trace --stats` for the
+per-kernel split (smooth_fwd_kernel, smooth_bwd_kernel, smoother_tables_kernel: --rebuild forces one table build per call)."""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from multioutputihgp_amd.streams import LatentBank  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--L", type=int, default=4096)
+    ap.add_argument("--T", type=int, default=10000)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--path", type=int, default=-1, help='option "smoother_path": -1 automatic, 0 scan kernels, 1 serial fp64')
+    ap.add_argument("--rebuild", action="store_true", help="rewrite the tables before every call (times the tables kernel too)")
+    a = ap.parse_args()
+    torch.cuda.set_device(0)
+    rng = np.random.default_rng(0)
+    prm = np.column_stack([rng.uniform(0.5, 2, a.L), rng.uniform(0.5, 2, a.L), rng.uniform(0.02, 0.3, a.L)])
+    bank = LatentBank(0.1, prm, kernel="Matern52ss")
+    bank.set_option("smoother_path", a.path)
+    flush = torch.empty(2 << 28, dtype=torch.float32, device="cuda")
+    for dt in (torch.float32, torch.float64):
+        es = 4 if dt == torch.float32 else 8
+        Ty = torch.randn((a.L, a.T), dtype=dt, device="cuda")
+        ys = torch.empty_like(Ty)
+        x = torch.zeros((a.L, bank.d), dtype=dt, device="cuda")
+        _, _, status = bank.smooth(Ty, x=x, ysmooth=ys)
+        torch.cuda.synchronize()
+        vf, vs = bank.latent_variances()
+        print(f"status != 0: {int((status != 0).sum())} latents; var_smoothed / var_filtered in [{np.min(vs / vf):.3f}, {np.max(vs / vf):.3f}]")
+        mb = a.L * a.T * es / 1e6
+        for cold in (False, True):
+            ts = []
+            for _ in range(a.iters):
+                if a.rebuild:
+                    bank.update(prm)
+                if cold:
+                    flush.fill_(1.0)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                bank.smooth(Ty, x=x, ysmooth=ys)
+                e1.record()
+                torch.cuda.synchronize()
+                ts.append(e0.elapsed_time(e1))
+            t = float(np.median(ts)) * 1e3
+            print(f"smooth {str(dt).split('.')[-1]} L={a.L} T={a.T} {'cold' if cold else 'resident'}: {t:.1f} us  "
+                  f"(traffic {2 * mb:.0f} MB + {3 * mb:.0f} MB -> {5 * mb * 1e6 / (t * 1e-6) / 1e12:.2f} TB/s)", flush=True)
+
+
+if __name__ == "__main__":
+    main()
