@@ -268,6 +268,44 @@ int moihgp_get_smoother(moihgp_gp* gp, size_t l, double* P, double* K, double* G
                         double* var_filtered, double* var_smoothed);
 int moihgp_latent_variances(moihgp_gp* gp, double* var_filtered, double* var_smoothed);
 
+/* ---- multi-horizon forecasts of whole streams, with variances (not in the reference, whose only route is the per-tick ABI: one step(x, y) and
+ * then h prediction-only step(x) calls per tick and per horizon, ihgp.h:96-100) --------------------------------------------------------------
+ * Per latent, A the handle's A, H = e0, and gains (K, M):
+ *     gains = MOIHGP_GAINS_KALMAN (0, the default of the host wrappers): K of the smoother's tables (the Kalman-form DARE of moihgp_smooth_stream),
+ *                                  M = A - K H A;
+ *     gains = MOIHGP_GAINS_HANDLE (1): the handle's K and AKHA (what moihgp_get_latent returns; the learners' filter, the reference's literal DARE).
+ * With x[-1] = x_in:   x[t] = M x[t-1] + K y[t],   or x[t] = A x[t-1] where y[t] is NaN.   For horizons h_0 .. h_{K-1}
+ * (0 <= h <= 2^20, 1 <= K <= MOIHGP_FORECAST_MAX_HORIZONS, need not be sorted or distinct):
+ *     fc[k][l][t] = H A^{h_k} x_l[t]        0 <= t < T
+ * i.e. plane k holds, AT THE INDEX OF THE TICK THE FORECAST WAS MADE AT, the mean of the latent at tick t + h_k given the ticks <= t.  h = 0 is the
+ * filtered mean (with gains = 1 it is moihgp_filter_stream's yhat).  A forecast is written at missing ticks too.  With the Kalman gains the interior
+ * of a long gap-free stream gives the exact GP predictive mean; the handle's gains give exactly "the reference's step followed by h prediction-only
+ * steps", which is off the GP predictive mean by what the literal DARE is off the Kalman one.
+ * Variances belong to the Kalman gains only (they are NOT the error of the literal-gain estimator):
+ *     var[k][l] = (Pinf - A^{h_k} (Pinf - PF) A^{h_k}^T)_00        Pinf the model's stationary covariance, PF the smoother's filtered covariance
+ * the steady-state variance of the latent FUNCTION at t + h given the ticks <= t; add R for an observation.  h = 0 equals var_filtered of
+ * moihgp_latent_variances; it rises monotonically to Pinf_00.
+ * moihgp_forecast_stream: Ty, x_in, x, ld_in, ld_out, alignment, asynchrony and stream bookkeeping as moihgp_smooth_stream (x_in == x allowed; fc
+ *   must not overlap Ty).  horizons: HOST int [K], read before the call returns.  Plane k starts k * plane_stride elements after fc;
+ *   plane_stride >= L * ld_out and a multiple of 16 bytes.  status: DEVICE int [L] or NULL.  gains = 0: a latent whose Kalman DARE did not converge
+ *   gets status 1, NaN in all its K rows and a NaN end state; the smoother's tables are built on the first such call after a table rewrite, exactly
+ *   as by a smooth.  gains = 1: status is all zero (the rows are whatever the handle's own tables give, as moihgp_filter_stream), and the smoother's
+ *   tables are neither needed nor built.  fp32 streams are swept in fp32 arithmetic, fp64 streams in fp64.  Returns 1 (and launches nothing) for K or
+ *   a horizon out of range, bad strides or alignment, an overlap, unknown gains; 3 for stacked models.
+ *   Option "forecast_path" (moihgp_set_option): -1 automatic (the time-parallel scan kernel; a serial fp64 walk for latents whose M fails a
+ *   growth bound -- the smoother's for fp64 streams, a tighter one for fp32; rho(AKHA) > 1 does occur with the handle's gains), 0 scan for every
+ *   latent, 1 serial fp64 walk for every latent.
+ * moihgp_forecast_tail: from any state x [L][d] (dtype), tail[l][j] = H A^{j+1} x_l, 0 <= j < n <= 2^20, tail [L][ld_out] (dtype): the forecast beyond
+ *   the end of a stream (depends on A only).  Asynchronous on `stream`.
+ * moihgp_forecast_variances: var [K][L] to a HOST buffer (NaN for a latent whose Kalman DARE did not converge).  Synchronises. */
+#define MOIHGP_FORECAST_MAX_HORIZONS 8
+enum { MOIHGP_GAINS_KALMAN = 0, MOIHGP_GAINS_HANDLE = 1 };
+int moihgp_forecast_stream(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x,
+                           const int* horizons, size_t K, void* fc, size_t ld_out, size_t plane_stride,
+                           int gains, int* status, void* stream);
+int moihgp_forecast_tail(moihgp_gp* gp, int dtype, const void* x, size_t n, void* tail, size_t ld_out, void* stream);
+int moihgp_forecast_variances(moihgp_gp* gp, const int* horizons, size_t K, double* var);
+
 /* As above plus the hyper-parameter sensitivities (ihgp.h:54) and the per-latent NLL gradient
  * (ihgp.h:216-220), summed over ticks:
  *   dx   [L][P][d] in/out (dtype);  grad [L][P] doubles out. */

@@ -149,6 +149,45 @@ public:
         for (size_t t = 0; t < T; t++) for (size_t m = 0; m < M; m++) Ys[t][m] = flat[t * M + m];
         return Ys;
     }
+    // (not in the reference) Forecasts `horizon` ticks ahead at every tick of the series with the current parameters (include/moihgp.h
+    // moihgp_forecast_stream, Kalman-form gains): element t is the mean of every output at tick t + horizon given Y[0..t], from a zero start
+    // state, where the reference would call step(x, y) and then `horizon` prediction-only steps per tick.  fp64 on the device:
+    // project_stream -> forecast_stream -> unproject_stream.  Throws std::invalid_argument for a horizon outside 0 .. 2^20 and std::runtime_error
+    // if a latent's Kalman DARE did not converge (status 1: its row would be NaN).  Missing outputs (NaN) are projected as in predictSmoothed().
+    std::vector<Vector> predictAhead(const std::vector<Vector>& Y, int horizon) {
+        if (horizon < 0 || horizon > (1 << 20)) throw std::invalid_argument("predictAhead: horizon must be 0 .. 2^20");
+        const size_t T = Y.size(), M = _num_output, L = _num_latent, ld = (T + 1) / 2 * 2;
+        std::vector<Vector> Yf(T, Vector(M, 0.0));
+        if (T == 0) return Yf;
+        Vector flat(T * M), zeros(L * _dim, 0.0);
+        for (size_t t = 0; t < T; t++) for (size_t m = 0; m < M; m++) flat[t * M + m] = Y[t][m];
+        moihgp_dvec_ctx* ctx = moihgp_dvec_ctx_new();
+        const size_t nst = (L + 1) / 2;                             // status words: L ints in doubles' storage
+        double *dY = moihgp_dvec_alloc(T * M), *dTy = moihgp_dvec_alloc(L * ld), *dfc = moihgp_dvec_alloc(L * ld), *dx = moihgp_dvec_alloc(L * _dim),
+               *dst = moihgp_dvec_alloc(nst);
+        int rc = (ctx && dY && dTy && dfc && dx && dst) ? 0 : 4;
+        Vector st(nst, 0.0);
+        void* s = ctx ? moihgp_dvec_ctx_stream(ctx) : nullptr;
+        moihgp_gp* h = _moihgp->handle();
+        if (!rc) rc = moihgp_dvec_upload(ctx, dY, flat.data(), T * M);
+        if (!rc) rc = moihgp_dvec_upload(ctx, dx, zeros.data(), L * _dim);
+        if (!rc) rc = moihgp_project_stream(h, MOIHGP_F64, dY, T, dTy, ld, s);
+        if (!rc) rc = moihgp_forecast_stream(h, MOIHGP_F64, dTy, T, ld, dx, dx, &horizon, 1, dfc, ld, L * ld, MOIHGP_GAINS_KALMAN,
+                                             reinterpret_cast<int*>(dst), s);
+        if (!rc) rc = moihgp_unproject_stream(h, MOIHGP_F64, dfc, T, ld, dY, s);
+        if (!rc) rc = moihgp_dvec_download(ctx, flat.data(), dY, T * M);
+        if (!rc) rc = moihgp_dvec_download(ctx, st.data(), dst, nst);
+        if (ctx) { moihgp_dvec_sync(ctx); moihgp_release_stream(h, s); }
+        for (double* p : {dY, dTy, dfc, dx, dst}) if (p) moihgp_dvec_free(p);
+        if (ctx) moihgp_dvec_ctx_del(ctx);
+        if (rc) throw std::runtime_error(std::string("predictAhead: ") + moihgp_last_error());
+        std::vector<int> status(2 * nst, 0);
+        std::memcpy(status.data(), st.data(), sizeof(double) * nst);
+        for (size_t l = 0; l < L; l++)
+            if (status[l] != 0) throw std::runtime_error("predictAhead: the Kalman DARE of latent " + std::to_string(l) + " did not converge");
+        for (size_t t = 0; t < T; t++) for (size_t m = 0; m < M; m++) Yf[t][m] = flat[t * M + m];
+        return Yf;
+    }
     Vector getParams() { return _moihgp->getParams(); }
     size_t getNumParam() { return _num_param; }
     size_t getNumOutput() { return _num_output; }

@@ -129,13 +129,21 @@ struct moihgp_gp {
     hipStream_t sm_built_on = nullptr;   // stream that carried the last build; sm_ev marks its end for the other streams / host reads
     hipEvent_t sm_ev = nullptr;
     int opt_smoother_path = -1;          // option "smoother_path": -1 automatic, 0 scan kernels, 1 serial fp64
+    // multi-horizon forecasts (moihgp_forecast_stream): the per-call tables (fp64 and fp32 copy), rebuilt by every call for its horizons on its
+    // stream; fc_ev marks the end of the last call that used them, and a call on another stream waits for it before it rewrites them
+    double* dfc64 = nullptr;
+    float* dfc32 = nullptr;
+    hipStream_t fc_last = nullptr;
+    hipEvent_t fc_ev = nullptr;
+    bool fc_ev_set = false;
+    int opt_forecast_path = -1;          // option "forecast_path": -1 automatic, 0 scan kernel, 1 serial fp64
 
     TickArgs tick() const { return TickArgs{d, M, L, cb64, dU, dS, dsqrtS, dinvsqrtS, dsigma, (threading || lik1_full) ? 1 : 0, P, cbd64}; }
 };
 
 static void gp_free(moihgp_gp* g) {
     if (!g) return;
-    void* ptrs[] = {g->dU, g->dS, g->dsqrtS, g->dinvsqrtS, g->dsigma, g->dparams, g->cb64, g->cb32, g->dx, g->dpart, g->dTy, g->dUty, g->dTyhat, g->dloss, g->dgrad, g->dscratch, g->dwork, g->dpolar, g->dfallback, g->dwin, g->dunstable, g->dxscratch, g->cbd64, g->dU32, g->dhp, g->dlink, g->dwinmiss, g->dtp64, g->dtp32, g->dxc64, g->dxc32, g->dlinkflags, g->dgap, g->drescue_idx, g->drescue, g->drescue_const, g->dsm};
+    void* ptrs[] = {g->dU, g->dS, g->dsqrtS, g->dinvsqrtS, g->dsigma, g->dparams, g->cb64, g->cb32, g->dx, g->dpart, g->dTy, g->dUty, g->dTyhat, g->dloss, g->dgrad, g->dscratch, g->dwork, g->dpolar, g->dfallback, g->dwin, g->dunstable, g->dxscratch, g->cbd64, g->dU32, g->dhp, g->dlink, g->dwinmiss, g->dtp64, g->dtp32, g->dxc64, g->dxc32, g->dlinkflags, g->dgap, g->drescue_idx, g->drescue, g->drescue_const, g->dsm, g->dfc64, g->dfc32};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (void* p : g->pinned) (void)hipHostUnregister(p);
@@ -146,6 +154,7 @@ static void gp_free(moihgp_gp* g) {
     for (hipEvent_t e : g->prof_ev) (void)hipEventDestroy(e);
     if (g->order_ev) (void)hipEventDestroy(g->order_ev);
     if (g->sm_ev) (void)hipEventDestroy(g->sm_ev);
+    if (g->fc_ev) (void)hipEventDestroy(g->fc_ev);
     if (g->stream) (void)hipStreamDestroy(g->stream);
     delete g;
 }
@@ -1015,6 +1024,109 @@ int moihgp_latent_variances(moihgp_gp* gp, double* var_filtered, double* var_smo
     return guard_rc([&] { return latent_variances_impl(gp, var_filtered, var_smoothed); });
 }
 
+// ---- multi-horizon forecasts (forecast.hip) -----------------------------------------------------------------------------------------------------
+// The tables depend on the call's horizons and gains, so every call builds them on its own stream into the handle's two buffers.
+static void forecast_begin(moihgp_gp* g, hipStream_t s) {
+    if (!g->dfc64) { g->dfc64 = dev_alloc<double>(g->L * (size_t)fc_size(g->d)); g->dfc32 = dev_alloc<float>(g->L * (size_t)fc_size(g->d)); }
+    if (!g->fc_ev) MOIHGP_HIP_FATAL(hipEventCreateWithFlags(&g->fc_ev, hipEventDisableTiming));
+    if (g->fc_ev_set && s != g->fc_last) MOIHGP_HIP_FATAL(hipStreamWaitEvent(s, g->fc_ev, 0));
+}
+static void forecast_end(moihgp_gp* g, hipStream_t s) {
+    g->fc_last = s;
+    g->fc_ev_set = true;
+    MOIHGP_HIP_FATAL(hipEventRecord(g->fc_ev, s));
+}
+
+static int check_horizons(const int* horizons, size_t K, FcHorizons& hz) {
+    if (K < 1 || K > (size_t)MOIHGP_FORECAST_MAX_HORIZONS) { set_last_error("forecast: the number of horizons (%zu) must be 1 .. %d", K, MOIHGP_FORECAST_MAX_HORIZONS); return 1; }
+    if (!horizons) { set_last_error("forecast: null horizons"); return 1; }
+    for (size_t k = 0; k < (size_t)kFcMaxHorizons; k++) hz.h[k] = 0;
+    for (size_t k = 0; k < K; k++) {
+        if (horizons[k] < 0 || horizons[k] > (1 << 20)) { set_last_error("forecast: horizon %zu (%d) must be 0 .. 2^20", k, horizons[k]); return 1; }
+        hz.h[k] = horizons[k];
+    }
+    return 0;
+}
+
+static int forecast_stream_impl(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x, const int* horizons, size_t K,
+                                void* fc, size_t ld_out, size_t plane_stride, int gains, int* status, void* stream) {
+    if (int rc = check_stream_args(gp, dtype, Ty, T, ld_in, x)) return rc;
+    if (!x_in) { set_last_error("null start state"); return 1; }
+    FcHorizons hz;
+    if (int rc = check_horizons(horizons, K, hz)) return rc;
+    if (gains != MOIHGP_GAINS_KALMAN && gains != MOIHGP_GAINS_HANDLE) { set_last_error("forecast: gains must be MOIHGP_GAINS_KALMAN (0) or MOIHGP_GAINS_HANDLE (1)"); return 1; }
+    const size_t es = dtype == MOIHGP_F64 ? 8 : 4, epv = 16 / es;
+    if (!fc && T > 0) { set_last_error("null forecast buffer"); return 1; }
+    if (fc && ((uintptr_t)fc & 15) != 0) { set_last_error("forecast buffer base must be 16-byte aligned"); return 1; }
+    if (fc && (ld_out % epv != 0 || ld_out < (T + epv - 1) / epv * epv)) {
+        set_last_error("ld_out (%zu) must be a multiple of %zu and >= T rounded up to it", ld_out, epv);
+        return 1;
+    }
+    if (fc && (plane_stride % epv != 0 || plane_stride < gp->L * ld_out)) {
+        set_last_error("plane_stride (%zu) must be a multiple of %zu and >= L * ld_out (%zu)", plane_stride, epv, gp->L * ld_out);
+        return 1;
+    }
+    if (fc && T > 0) {   // a segment of y is read after earlier segments' planes were written: the two may not overlap
+        const uintptr_t a0 = (uintptr_t)Ty, a1 = a0 + gp->L * ld_in * es, b0 = (uintptr_t)fc, b1 = b0 + ((K - 1) * plane_stride + gp->L * ld_out) * es;
+        if (a0 < b1 && b0 < a1) { set_last_error("the forecast buffer must not overlap the input stream"); return 1; }
+    }
+    if (kernel_stack(gp->kernel)) { set_last_error("forecast: stacked models are not supported (Matern-3/2 and -5/2 only)"); return 3; }
+    hipStream_t s = (hipStream_t)stream;
+    if (gains == MOIHGP_GAINS_KALMAN)
+        if (int rc = ensure_smoother(gp, s)) return rc;
+    note_user_stream(gp, s);
+    forecast_begin(gp, s);
+    launch_forecast_tables(kernel_base(gp->kernel), gp->d, gp->cb64, gp->dsm, gp->L, hz, (int)K, gains, gp->dfc64, gp->dfc32, s);
+    launch_forecast_stream(gp->d, dtype, Ty, T, ld_in, gp->L, gp->dfc64, gp->dfc32, x_in, x, fc, ld_out, plane_stride, (int)K, status,
+                           gp->opt_forecast_path, s);
+    forecast_end(gp, s);
+    return 0;
+}
+
+static int forecast_tail_impl(moihgp_gp* gp, int dtype, const void* x, size_t n, void* tail, size_t ld_out, void* stream) {
+    if (!gp) { set_last_error("null handle"); return 1; }
+    if (dtype != MOIHGP_F64 && dtype != MOIHGP_F32) { set_last_error("dtype must be MOIHGP_F64 or MOIHGP_F32"); return 1; }
+    if (!x || (n > 0 && !tail)) { set_last_error("forecast_tail: null state/tail pointer"); return 1; }
+    if (n > ((size_t)1 << 20)) { set_last_error("forecast_tail: n (%zu) must be <= 2^20", n); return 1; }
+    const size_t epv = dtype == MOIHGP_F64 ? 2 : 4;
+    if (((uintptr_t)tail & 15) != 0) { set_last_error("tail base must be 16-byte aligned"); return 1; }
+    if (ld_out % epv != 0 || ld_out < (n + epv - 1) / epv * epv) { set_last_error("ld_out (%zu) must be a multiple of %zu and >= n rounded up to it", ld_out, epv); return 1; }
+    if (kernel_stack(gp->kernel)) { set_last_error("forecast: stacked models are not supported (Matern-3/2 and -5/2 only)"); return 3; }
+    hipStream_t s = (hipStream_t)stream;
+    note_user_stream(gp, s);
+    launch_forecast_tail(gp->d, dtype, gp->cb64, gp->L, x, n, tail, ld_out, s);
+    return 0;
+}
+
+static int forecast_variances_impl(moihgp_gp* gp, const int* horizons, size_t K, double* var) {
+    if (!gp) { set_last_error("null handle"); return 1; }
+    FcHorizons hz;
+    if (int rc = check_horizons(horizons, K, hz)) return rc;
+    if (int rc = ensure_smoother(gp, gp->stream)) return rc;
+    if (!var) return 0;
+    forecast_begin(gp, gp->stream);
+    launch_forecast_tables(kernel_base(gp->kernel), gp->d, gp->cb64, gp->dsm, gp->L, hz, (int)K, MOIHGP_GAINS_KALMAN, gp->dfc64, gp->dfc32, gp->stream);
+    const size_t bs = (size_t)fc_size(gp->d), vo = (size_t)fc_var_offset(gp->d);
+    std::vector<double> b(gp->L * bs);
+    MOIHGP_HIP_FATAL(hipMemcpyAsync(b.data(), gp->dfc64, sizeof(double) * b.size(), hipMemcpyDeviceToHost, gp->stream));
+    forecast_end(gp, gp->stream);
+    MOIHGP_HIP_FATAL(hipStreamSynchronize(gp->stream));
+    for (size_t k = 0; k < K; k++)
+        for (size_t l = 0; l < gp->L; l++) var[k * gp->L + l] = b[l * bs + vo + k];
+    return 0;
+}
+
+int moihgp_forecast_stream(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x, const int* horizons, size_t K,
+                           void* fc, size_t ld_out, size_t plane_stride, int gains, int* status, void* stream) {
+    return guard_rc([&] { return forecast_stream_impl(gp, dtype, Ty, T, ld_in, x_in, x, horizons, K, fc, ld_out, plane_stride, gains, status, stream); });
+}
+int moihgp_forecast_tail(moihgp_gp* gp, int dtype, const void* x, size_t n, void* tail, size_t ld_out, void* stream) {
+    return guard_rc([&] { return forecast_tail_impl(gp, dtype, x, n, tail, ld_out, stream); });
+}
+int moihgp_forecast_variances(moihgp_gp* gp, const int* horizons, size_t K, double* var) {
+    return guard_rc([&] { return forecast_variances_impl(gp, horizons, K, var); });
+}
+
 int moihgp_stream_retile(int dtype, const void* src, void* dst, size_t L, size_t T, size_t ld, int to_tiled, void* stream) {
     return guard_rc([&] {
         if (dtype != MOIHGP_F64 && dtype != MOIHGP_F32) { set_last_error("dtype must be MOIHGP_F64 or MOIHGP_F32"); return 1; }
@@ -1303,6 +1415,7 @@ int moihgp_release_stream(moihgp_gp* gp, void* stream) {
             MOIHGP_HIP_FATAL(hipEventRecord(gp->order_ev, s));
             MOIHGP_HIP_FATAL(hipStreamWaitEvent(gp->stream, gp->order_ev, 0));
             gp->user_streams.erase(gp->user_streams.begin() + (long)i);
+            if (gp->fc_last == s) gp->fc_last = gp->stream;   // (the handle's stream now follows s: a later forecast on any other stream waits for fc_ev)
             break;
         }
         return 0;
@@ -1319,6 +1432,7 @@ int moihgp_set_option(moihgp_gp* gp, const char* name, long value) {
     if (n == "filter_team") { if (value < -1 || value > 2) { set_last_error("filter_team: -1 (automatic), 0 (never), 1 (whenever the stream fits), 2 (the 32-tick-chunk form only)"); return 1; } gp->opt_filter_team = (int)value; return 0; }
     if (n == "filter_maxlinks") { if (value < -1 || value > 64) { set_last_error("filter_maxlinks: -1 (automatic) .. 64"); return 1; } gp->opt_filter_maxlinks = (int)value; return 0; }
     if (n == "smoother_path") { if (value < -1 || value > 1) { set_last_error("smoother_path: -1 (automatic), 0 (scan kernels), 1 (serial fp64)"); return 1; } gp->opt_smoother_path = (int)value; return 0; }
+    if (n == "forecast_path") { if (value < -1 || value > 1) { set_last_error("forecast_path: -1 (automatic), 0 (scan kernel), 1 (serial fp64)"); return 1; } gp->opt_forecast_path = (int)value; return 0; }
     if (n == "filter_variant") {
 #ifdef MOIHGP_TUNING
         gp->opt_filter_variant = (int)value; return 0;

@@ -201,6 +201,18 @@ void launch_smoother_tables(int kernel, int d, const double* cb64, size_t L, dou
 // path: -1 automatic (scan kernels for the latents that pass the growth bound), 0 scan kernels, 1 serial fp64 for every latent
 void launch_smooth_stream(int d, int dtype, const void* Ty, size_t T, size_t ld_in, size_t L, const double* tabs, const void* x_in, void* x,
                           void* ys, size_t ld_out, int* status, int path, hipStream_t stream);
+// forecast.hip: multi-horizon forecasts (include/moihgp.h moihgp_forecast_stream).  Per-latent block of fc_size(d) scalars, built per call for the
+// call's horizons, as an fp64 and an fp32 copy; sm: the smoother's blocks (gains 0: Kalman-form K, A - K H A, PF) or unused (gains 1: the handle's).
+constexpr int kFcMaxHorizons = 8;   // MOIHGP_FORECAST_MAX_HORIZONS
+struct FcHorizons { int h[kFcMaxHorizons]; };
+int fc_size(int d);
+int fc_var_offset(int d);
+void launch_forecast_tables(int kernel, int d, const double* cb64, const double* sm, size_t L, const FcHorizons& hz, int K, int gains, double* t64,
+                            float* t32, hipStream_t stream);
+// path: -1 automatic (the scan for the latents that pass the growth bound), 0 scan for every latent, 1 serial fp64 for every latent
+void launch_forecast_stream(int d, int dtype, const void* Ty, size_t T, size_t ld_in, size_t L, const double* t64, const float* t32, const void* x_in,
+                            void* x, void* fc, size_t ld_out, size_t plane_stride, int K, int* status, int path, hipStream_t stream);
+void launch_forecast_tail(int d, int dtype, const double* cb64, size_t L, const void* x, size_t n, void* tail, size_t ld_out, hipStream_t stream);
 // series-major [L][ld] <-> segment-major [ceil(T / SEG)][L][SEG] (to_tiled != 0: src is series-major; ticks past T are written as zeros)
 int launch_stream_retile(int dtype, const void* src, void* dst, size_t L, size_t T, size_t ld, int to_tiled, hipStream_t stream);
 // recursion.hip: batched sweeps over series-major streams.

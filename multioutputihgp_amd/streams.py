@@ -81,6 +81,51 @@ def untile_stream(Tt: torch.Tensor, T: int, out: Optional[torch.Tensor] = None, 
     return out
 
 
+FORECAST_MAX_HORIZONS = 8       # MOIHGP_FORECAST_MAX_HORIZONS
+_GAINS = {"kalman": 0, "handle": 1}
+
+
+def _forecast_horizons(horizons):
+    """(ctypes int array, K) of a forecast's horizons, validated as include/moihgp.h states them."""
+    try:
+        hs = [h for h in horizons]
+    except TypeError:
+        raise ValueError("horizons must be a sequence of 1 .. 8 integers") from None
+    if not 1 <= len(hs) <= FORECAST_MAX_HORIZONS:
+        raise ValueError(f"the number of horizons ({len(hs)}) must be 1 .. {FORECAST_MAX_HORIZONS}")
+    for h in hs:
+        if isinstance(h, bool) or not isinstance(h, (int, np.integer)) or h < 0 or h > (1 << 20):
+            raise ValueError(f"horizon {h!r} must be an integer in 0 .. 2^20")
+    return (C.c_int * len(hs))(*[int(h) for h in hs]), len(hs)
+
+
+def _forecast_gains(gains) -> int:
+    if gains not in _GAINS:
+        raise ValueError('gains must be "kalman" or "handle"')
+    return _GAINS[gains]
+
+
+def _forecast_out_strides(out: torch.Tensor, K: int, L: int, T: int, Ty: torch.Tensor):
+    """(ld_out, plane_stride) of a forecast buffer [K, L, >=T] for the stream Ty, or ValueError: dtype, device, shape, unit stride along time, row and
+    plane strides multiples of 16 bytes, rows >= T rounded up, planes >= L rows, and no overlap with Ty."""
+    epv = 2 if Ty.dtype == torch.float64 else 4
+    ok = (out.device == Ty.device and out.dtype == Ty.dtype and out.dim() == 3 and out.shape[0] == K and out.shape[1] == L and out.shape[2] >= T
+          and (out.shape[2] <= 1 or out.stride(2) == 1) and out.data_ptr() % 16 == 0)
+    if ok:
+        ld_out = out.stride(1) if L > 1 else padded_len(max(T, 1), Ty.dtype)
+        plane = out.stride(0) if K > 1 else L * ld_out
+        ok = ld_out % epv == 0 and ld_out >= padded_len(T, Ty.dtype) and plane % epv == 0 and plane >= L * ld_out
+    if not ok:
+        raise ValueError("out must be a tensor [K, L, >=T] of the stream's dtype and device, 16-byte aligned, unit stride along time, row stride a "
+                         "multiple of 16 bytes and >= T rounded up to it, plane stride a multiple of 16 bytes and >= L rows")
+    es = Ty.element_size()
+    a0, a1 = Ty.data_ptr(), Ty.data_ptr() + L * Ty.stride(0) * es
+    b0, b1 = out.data_ptr(), out.data_ptr() + ((K - 1) * plane + L * ld_out) * es
+    if T > 0 and a0 < b1 and b0 < a1:
+        raise ValueError("out must not overlap the input stream")
+    return ld_out, plane
+
+
 class LatentBank:
     """A shard of independent latent IHGPs (reference include/moihgp/ihgp.h `IHGP<SS>` x L) on one GPU.
 
@@ -128,7 +173,7 @@ class LatentBank:
 
     def set_option(self, name: str, value: int):
         """Per-handle tuning / test hooks (include/moihgp.h moihgp_set_option): "filter_split" (0 automatic, 1 off, n slices),
-        "filter_maxlinks", "filter_variant" (tuning builds only)."""
+        "filter_maxlinks", "filter_variant" (tuning builds only), "smoother_path", "forecast_path" (-1 automatic, 0 scan kernels, 1 serial fp64)."""
         _check(self._lib.moihgp_set_option(self._h, name.encode(), int(value)), self._lib)
 
     def update(self, params_LP):
@@ -311,6 +356,59 @@ class LatentBank:
         return vf, vs
 
 
+    def forecast(self, Ty: torch.Tensor, horizons, T: Optional[int] = None, x: Optional[torch.Tensor] = None, x_start: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None, gains: str = "kalman", stream=None):
+        """Forecasts at every tick of T ticks for every latent (include/moihgp.h moihgp_forecast_stream): fc[k, l, t] is the mean of latent l at tick
+        t + horizons[k] given the ticks <= t, stored at the tick the forecast is made at (missing ticks included).  horizons: 1 .. 8 ints in
+        0 .. 2^20, in any order.  gains "kalman" (default): the smoother's Kalman-form gains, the GP predictive mean in the interior of a stream, with
+        forecast_variances() as its variance; "handle": the handle's own gains, i.e. filter()'s estimator followed by h prediction-only steps.
+
+        Returns (fc [K, L, >=T], x [L, d] end state, status [L] int32: 0 ok, 1 Kalman DARE not converged (rows NaN; always 0 with "handle")).
+        Asynchronous on the current torch stream.  The sweep starts from `x_start` if given, else from `x`, else from zeros; `x` receives the end
+        state in place.  `out` (optional) [K, L, >=T] must not overlap Ty; row and plane strides multiples of 16 bytes."""
+        T, ld = self._check_stream(Ty, T)
+        hz, K = _forecast_horizons(horizons)
+        g = _forecast_gains(gains)
+        if self.stacked:
+            raise MoihgpError("forecast: stacked models are not supported (Matern-3/2 and -5/2 only)", 3)
+        if x is None:
+            x = torch.zeros((self.L, self.d), dtype=Ty.dtype, device=Ty.device)
+        for name, t in (("x", x), ("x_start", x_start)):
+            if t is not None and (t.dtype != Ty.dtype or not t.is_contiguous() or tuple(t.shape) != (self.L, self.d)):
+                raise ValueError(f"{name} must be a contiguous [L, d] tensor of the stream dtype")
+        if out is None:
+            out = torch.empty((K, self.L, padded_len(max(T, 1), Ty.dtype)), dtype=Ty.dtype, device=Ty.device)[:, :, :T]
+        ld_out, plane = _forecast_out_strides(out, K, self.L, T, Ty)
+        status = torch.empty((self.L,), dtype=torch.int32, device=Ty.device)
+        rc = self._lib.moihgp_forecast_stream(self._h, _DT[Ty.dtype], C.c_void_p(Ty.data_ptr()), T, ld,
+                                              C.c_void_p((x if x_start is None else x_start).data_ptr()), C.c_void_p(x.data_ptr()), hz, K,
+                                              C.c_void_p(out.data_ptr()), ld_out, plane, g, C.c_void_p(status.data_ptr()), _stream_ptr(stream))
+        _check(rc, self._lib)
+        return out, x, status
+
+    def forecast_tail(self, x: torch.Tensor, n: int, stream=None) -> torch.Tensor:
+        """tail[l, j] = H A^(j+1) x_l, 0 <= j < n (moihgp_forecast_tail): the forecast beyond the end of a stream from its end state x [L, d]."""
+        n = int(n)
+        if n < 0 or n > (1 << 20):
+            raise ValueError("n must be 0 .. 2^20")
+        if x.dtype not in _DT or not x.is_contiguous() or tuple(x.shape) != (self.L, self.d):
+            raise ValueError("x must be a contiguous [L, d] tensor (float32/float64)")
+        if self.stacked:
+            raise MoihgpError("forecast: stacked models are not supported (Matern-3/2 and -5/2 only)", 3)
+        tail = alloc_stream(self.L, max(n, 1), x.dtype, x.device)
+        _check(self._lib.moihgp_forecast_tail(self._h, _DT[x.dtype], C.c_void_p(x.data_ptr()), n, C.c_void_p(tail.data_ptr()), tail.stride(0),
+                                              _stream_ptr(stream)), self._lib)
+        return tail[:, :n]
+
+    def forecast_variances(self, horizons) -> np.ndarray:
+        """var [K, L] (moihgp_forecast_variances), fp64 numpy: the steady-state variance of the latent function at t + h given the ticks <= t, which
+        belongs to the "kalman" gains (add the noise parameter for an observation); NaN for a latent whose Kalman DARE did not converge."""
+        hz, K = _forecast_horizons(horizons)
+        var = np.zeros((K, self.L))
+        _check(self._lib.moihgp_forecast_variances(self._h, hz, K, var.ctypes.data_as(c_double_p)), self._lib)
+        return var
+
+
 def project_stream(gp, Y: torch.Tensor, stream=None) -> torch.Tensor:
     """OILMM projection of a tick-major observation stream Y [T, M] with the mixing of `gp`
     (a pywrapper.MOIHGP): returns the series-major projected stream [L, ld] (moihgp.h:181 per tick)."""
@@ -355,3 +453,33 @@ def smooth_outputs(gp, Y: torch.Tensor, stream=None):
     U, S = prm[:M * L].reshape(M, L), prm[M * L:M * L + L]
     _, vs = bank.latent_variances()
     return Ys, (U ** 2) @ (S * vs)
+
+
+def forecast_outputs(gp, Y: torch.Tensor, horizons, tail: int = 0, gains: str = "kalman", stream=None):
+    """Forecasts of a tick-major observation stream Y [T, M] (NaN = missing output) with the parameters of `gp` (a pywrapper.MOIHGP), from a zero
+    state: project_stream -> LatentBank.forecast -> unproject_stream per horizon.
+
+    Returns (Yf [K, T, M] in Y's dtype, var_Y [K, M] fp64 numpy, Ytail [tail, M] or None).  Yf[k, t] is the mean of the outputs at tick
+    t + horizons[k] given the ticks <= t (stored at the tick the forecast is made at); Ytail[j] the mean at tick T + j given all T ticks.
+    var_Y[k, m] = sum_l U[m, l]^2 S_l var[k, l]: the steady-state variance of the latent FUNCTION at output m, without the observation noise; it
+    belongs to gains "kalman" and is returned unchanged with "handle", whose error it does not describe.  Raises MoihgpError if any latent's Kalman
+    DARE did not converge.  Ticks with missing outputs are projected as project_stream does it: a tick with more than 64 missing outputs or fewer
+    than L observed ones is treated as missing as a whole."""
+    T = Y.shape[0]
+    bank = LatentBank.from_handle(gp)
+    _, K = _forecast_horizons(horizons)
+    Ty = project_stream(gp, Y, stream=stream)
+    fc, x, status = bank.forecast(Ty, horizons, T=T, gains=gains, stream=stream)
+    Yf = torch.stack([unproject_stream(gp, fc[k], T, stream=stream) for k in range(K)])
+    Ytail = None
+    if tail:
+        Ytail = unproject_stream(gp, bank.forecast_tail(x, tail, stream=stream), tail, stream=stream)
+    var = bank.forecast_variances(horizons)      # (synchronises)
+    bad = int(((status != 0).cpu().numpy() | np.isnan(var).any(axis=0)).sum())
+    if bad:      # (with gains "handle" the means exist, but var_Y does not)
+        raise MoihgpError(f"forecast_outputs: the Kalman DARE of {bad} latent(s) did not converge; their rows and variances are NaN and so is "
+                          "every output that mixes them", 1)
+    M, L = gp.num_output, gp.num_latent
+    prm = gp.params
+    U, S = prm[:M * L].reshape(M, L), prm[M * L:M * L + L]
+    return Yf, (S[None, :] * var) @ (U ** 2).T, Ytail
