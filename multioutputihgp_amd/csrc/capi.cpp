@@ -6,6 +6,7 @@
 // factor of the mixing matrix in update() (moihgp.h:433-447); the host draws the constructor's random matrix and moves bytes.
 #include "../../include/moihgp.h"
 #include "common.h"
+#include "stream_tables.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -954,21 +955,34 @@ static int ensure_smoother(moihgp_gp* g, hipStream_t s) {
     return 0;
 }
 
+// One output row buffer of a whole-stream call: non-null where there is something to write, 16-byte aligned, rows ld_out scalars (of es bytes) apart
+// with ld_out a multiple of the 16-byte vector and >= n rounded up to it.  name, n_name: the entry's words for the buffer and for n in the error
+// texts; ld_of_null: the stride is checked even where a NULL buffer is allowed.
+static int check_out_rows(const void* out, const char* name, size_t n, char n_name, size_t ld_out, size_t es, bool ld_of_null = false) {
+    const size_t epv = 16 / es;
+    if (!out && n > 0) { set_last_error("null %s", name); return 1; }
+    if (((uintptr_t)out & 15) != 0) { set_last_error("%s base must be 16-byte aligned", name); return 1; }
+    if ((out || ld_of_null) && (ld_out % epv != 0 || ld_out < (n + epv - 1) / epv * epv)) {
+        set_last_error("ld_out (%zu) must be a multiple of %zu and >= %c rounded up to it", ld_out, epv, n_name);
+        return 1;
+    }
+    return 0;
+}
+// ... which may not overlap the input stream (in_elems, out_elems scalars of es bytes; nothing to check without output or ticks)
+static int check_no_overlap(const void* in, size_t in_elems, const void* out, size_t out_elems, size_t T, size_t es, const char* msg) {
+    const uintptr_t a0 = (uintptr_t)in, a1 = a0 + in_elems * es, b0 = (uintptr_t)out, b1 = b0 + out_elems * es;
+    if (out && T > 0 && a0 < b1 && b0 < a1) { set_last_error("%s", msg); return 1; }
+    return 0;
+}
+
 static int smooth_stream_impl(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x, void* ys, size_t ld_out,
                               int* status, void* stream) {
     if (int rc = check_stream_args(gp, dtype, Ty, T, ld_in, x)) return rc;
     if (!x_in) { set_last_error("null start state"); return 1; }
-    const size_t es = dtype == MOIHGP_F64 ? 8 : 4, epv = 16 / es;
-    if (!ys && T > 0) { set_last_error("null ysmooth"); return 1; }
-    if (ys && ((uintptr_t)ys & 15) != 0) { set_last_error("ysmooth base must be 16-byte aligned"); return 1; }
-    if (ys && (ld_out % epv != 0 || ld_out < (T + epv - 1) / epv * epv)) {
-        set_last_error("ld_out (%zu) must be a multiple of %zu and >= T rounded up to it", ld_out, epv);
-        return 1;
-    }
-    if (ys && T > 0) {   // the backward sweep reads y after the forward one wrote the predicted means: the two may not overlap
-        const uintptr_t a0 = (uintptr_t)Ty, a1 = a0 + gp->L * ld_in * es, b0 = (uintptr_t)ys, b1 = b0 + gp->L * ld_out * es;
-        if (a0 < b1 && b0 < a1) { set_last_error("ysmooth must not overlap the input stream"); return 1; }
-    }
+    const size_t es = dtype == MOIHGP_F64 ? 8 : 4;
+    if (int rc = check_out_rows(ys, "ysmooth", T, 'T', ld_out, es)) return rc;
+    // the backward sweep reads y after the forward one wrote the predicted means: the two may not overlap
+    if (int rc = check_no_overlap(Ty, gp->L * ld_in, ys, gp->L * ld_out, T, es, "ysmooth must not overlap the input stream")) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (int rc = ensure_smoother(gp, s)) return rc;
     note_user_stream(gp, s);
@@ -991,11 +1005,12 @@ static int get_smoother_impl(moihgp_gp* gp, size_t l, double* P, double* K, doub
     if (!gp || l >= gp->L) { set_last_error("get_smoother: bad latent index"); return 1; }
     std::vector<double> b;
     if (int rc = read_smoother(gp, l, 1, b)) return rc;
-    int off[14];
-    sm_offsets(gp->d, off);
-    const int d = gp->d, nn = d * d;
     auto cp = [&](double* dst, int o, int n) { if (dst) std::memcpy(dst, b.data() + o, sizeof(double) * n); };
-    cp(P, off[6], nn); cp(K, off[2], d); cp(G, off[3], nn); cp(Ps, off[8], nn); cp(var_f, off[9], 1); cp(var_s, off[10], 1);
+    dispatch_dim(gp->d, [&](auto dim) {
+        constexpr int D = decltype(dim)::value;
+        using B = SM<D>;
+        cp(P, B::P, B::NN); cp(K, B::K, D); cp(G, B::G, B::NN); cp(Ps, B::PS, B::NN); cp(var_f, B::VARF, 1); cp(var_s, B::VARS, 1);
+    });
     return 0;
 }
 
@@ -1003,13 +1018,13 @@ static int latent_variances_impl(moihgp_gp* gp, double* var_f, double* var_s) {
     if (!gp) { set_last_error("null handle"); return 1; }
     std::vector<double> b;
     if (int rc = read_smoother(gp, 0, gp->L, b)) return rc;
-    int off[14];
-    sm_offsets(gp->d, off);
-    const size_t bs = (size_t)sm_size(gp->d);
-    for (size_t l = 0; l < gp->L; l++) {
-        if (var_f) var_f[l] = b[l * bs + off[9]];
-        if (var_s) var_s[l] = b[l * bs + off[10]];
-    }
+    dispatch_dim(gp->d, [&](auto dim) {
+        using B = SM<decltype(dim)::value>;
+        for (size_t l = 0; l < gp->L; l++) {
+            if (var_f) var_f[l] = b[l * B::SIZE + B::VARF];
+            if (var_s) var_s[l] = b[l * B::SIZE + B::VARS];
+        }
+    });
     return 0;
 }
 
@@ -1056,20 +1071,13 @@ static int forecast_stream_impl(moihgp_gp* gp, int dtype, const void* Ty, size_t
     if (int rc = check_horizons(horizons, K, hz)) return rc;
     if (gains != MOIHGP_GAINS_KALMAN && gains != MOIHGP_GAINS_HANDLE) { set_last_error("forecast: gains must be MOIHGP_GAINS_KALMAN (0) or MOIHGP_GAINS_HANDLE (1)"); return 1; }
     const size_t es = dtype == MOIHGP_F64 ? 8 : 4, epv = 16 / es;
-    if (!fc && T > 0) { set_last_error("null forecast buffer"); return 1; }
-    if (fc && ((uintptr_t)fc & 15) != 0) { set_last_error("forecast buffer base must be 16-byte aligned"); return 1; }
-    if (fc && (ld_out % epv != 0 || ld_out < (T + epv - 1) / epv * epv)) {
-        set_last_error("ld_out (%zu) must be a multiple of %zu and >= T rounded up to it", ld_out, epv);
-        return 1;
-    }
+    if (int rc = check_out_rows(fc, "forecast buffer", T, 'T', ld_out, es)) return rc;
     if (fc && (plane_stride % epv != 0 || plane_stride < gp->L * ld_out)) {
         set_last_error("plane_stride (%zu) must be a multiple of %zu and >= L * ld_out (%zu)", plane_stride, epv, gp->L * ld_out);
         return 1;
     }
-    if (fc && T > 0) {   // a segment of y is read after earlier segments' planes were written: the two may not overlap
-        const uintptr_t a0 = (uintptr_t)Ty, a1 = a0 + gp->L * ld_in * es, b0 = (uintptr_t)fc, b1 = b0 + ((K - 1) * plane_stride + gp->L * ld_out) * es;
-        if (a0 < b1 && b0 < a1) { set_last_error("the forecast buffer must not overlap the input stream"); return 1; }
-    }
+    // a segment of y is read after earlier segments' planes were written: the two may not overlap
+    if (int rc = check_no_overlap(Ty, gp->L * ld_in, fc, (K - 1) * plane_stride + gp->L * ld_out, T, es, "the forecast buffer must not overlap the input stream")) return rc;
     if (kernel_stack(gp->kernel)) { set_last_error("forecast: stacked models are not supported (Matern-3/2 and -5/2 only)"); return 3; }
     hipStream_t s = (hipStream_t)stream;
     if (gains == MOIHGP_GAINS_KALMAN)
@@ -1088,9 +1096,7 @@ static int forecast_tail_impl(moihgp_gp* gp, int dtype, const void* x, size_t n,
     if (dtype != MOIHGP_F64 && dtype != MOIHGP_F32) { set_last_error("dtype must be MOIHGP_F64 or MOIHGP_F32"); return 1; }
     if (!x || (n > 0 && !tail)) { set_last_error("forecast_tail: null state/tail pointer"); return 1; }
     if (n > ((size_t)1 << 20)) { set_last_error("forecast_tail: n (%zu) must be <= 2^20", n); return 1; }
-    const size_t epv = dtype == MOIHGP_F64 ? 2 : 4;
-    if (((uintptr_t)tail & 15) != 0) { set_last_error("tail base must be 16-byte aligned"); return 1; }
-    if (ld_out % epv != 0 || ld_out < (n + epv - 1) / epv * epv) { set_last_error("ld_out (%zu) must be a multiple of %zu and >= n rounded up to it", ld_out, epv); return 1; }
+    if (int rc = check_out_rows(tail, "tail", n, 'n', ld_out, dtype == MOIHGP_F64 ? 8 : 4, true)) return rc;
     if (kernel_stack(gp->kernel)) { set_last_error("forecast: stacked models are not supported (Matern-3/2 and -5/2 only)"); return 3; }
     hipStream_t s = (hipStream_t)stream;
     note_user_stream(gp, s);
@@ -1106,7 +1112,7 @@ static int forecast_variances_impl(moihgp_gp* gp, const int* horizons, size_t K,
     if (!var) return 0;
     forecast_begin(gp, gp->stream);
     launch_forecast_tables(kernel_base(gp->kernel), gp->d, gp->cb64, gp->dsm, gp->L, hz, (int)K, MOIHGP_GAINS_KALMAN, gp->dfc64, gp->dfc32, gp->stream);
-    const size_t bs = (size_t)fc_size(gp->d), vo = (size_t)fc_var_offset(gp->d);
+    const size_t bs = (size_t)fc_size(gp->d), vo = (size_t)(gp->d == 2 ? FT<2>::VAR : FT<3>::VAR);
     std::vector<double> b(gp->L * bs);
     MOIHGP_HIP_FATAL(hipMemcpyAsync(b.data(), gp->dfc64, sizeof(double) * b.size(), hipMemcpyDeviceToHost, gp->stream));
     forecast_end(gp, gp->stream);

@@ -193,20 +193,16 @@ int launch_gap_impulse(const GapBank& b, int kernel, int dtype, size_t L, const 
 // recursion.hip: the same sweep over segment-major streams [ceil(T / SEG)][L][SEG], SEG = 4096 / sizeof(scalar) ticks (d = 2, 3)
 int launch_filter_stream_tiled(int d, int dtype, const void* Ty, size_t T, size_t L, const double* cb64, const float* cb32, const void* xin, void* x,
                                void* yhat, double* nll, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, int n_unstable, double* total, int variant = 0);
-// smoother.hip: steady-state RTS smoothing (include/moihgp.h moihgp_smooth_stream).  Per-latent fp64 block of sm_size(d) doubles;
-// sm_offsets fills 14 offsets: A AKHA K G MF MB P PF PS VARF VARS GROWTH RESID STATUS.
-int sm_size(int d);
-void sm_offsets(int d, int* off);
+// smoother.hip: steady-state RTS smoothing (include/moihgp.h moihgp_smooth_stream).  Per-latent fp64 block SM<D> of sm_size(d) doubles
+// (stream_tables.h, which names its fields).
 void launch_smoother_tables(int kernel, int d, const double* cb64, size_t L, double* tabs, hipStream_t stream);
 // path: -1 automatic (scan kernels for the latents that pass the growth bound), 0 scan kernels, 1 serial fp64 for every latent
 void launch_smooth_stream(int d, int dtype, const void* Ty, size_t T, size_t ld_in, size_t L, const double* tabs, const void* x_in, void* x,
                           void* ys, size_t ld_out, int* status, int path, hipStream_t stream);
-// forecast.hip: multi-horizon forecasts (include/moihgp.h moihgp_forecast_stream).  Per-latent block of fc_size(d) scalars, built per call for the
-// call's horizons, as an fp64 and an fp32 copy; sm: the smoother's blocks (gains 0: Kalman-form K, A - K H A, PF) or unused (gains 1: the handle's).
+// forecast.hip: multi-horizon forecasts (include/moihgp.h moihgp_forecast_stream).  Per-latent block FT<D> of fc_size(d) scalars (stream_tables.h), built
+// per call for the call's horizons, as an fp64 and an fp32 copy; sm: the smoother's blocks (gains 0: Kalman-form K, A - K H A, PF) or unused (gains 1: the handle's).
 constexpr int kFcMaxHorizons = 8;   // MOIHGP_FORECAST_MAX_HORIZONS
 struct FcHorizons { int h[kFcMaxHorizons]; };
-int fc_size(int d);
-int fc_var_offset(int d);
 void launch_forecast_tables(int kernel, int d, const double* cb64, const double* sm, size_t L, const FcHorizons& hz, int K, int gains, double* t64,
                             float* t32, hipStream_t stream);
 // path: -1 automatic (the scan for the latents that pass the growth bound), 0 scan for every latent, 1 serial fp64 for every latent

@@ -36,6 +36,30 @@ __device__ inline void mv(const double* A, const double* x, double* y) {
     for (int i = 0; i < N; i++) y[i] = T[i];
 }
 template <int N>
+__device__ inline double norm_inf(const double* X) {
+    double m = 0.0;
+    for (int i = 0; i < N; i++) {
+        double s = 0.0;
+        for (int j = 0; j < N; j++) s += fabs(X[i * N + j]);
+        m = fmax(m, s);
+    }
+    return m;
+}
+// Xc <- X^C and Xp <- X^(2C) by repeated multiplication from the left; returns the largest inf-norm of X^1 .. X^(2C) (fmax drops a NaN
+// operand: a caller that must notice one tests the powers)
+template <int N, int C>
+__device__ inline double chunk_powers(const double* X, double* Xc, double* Xp) {
+    double growth = 0.0;
+    for (int i = 0; i < N * N; i++) Xp[i] = X[i];
+#pragma nounroll
+    for (int p = 1;; p++) {
+        if (p == C) for (int i = 0; i < N * N; i++) Xc[i] = Xp[i];
+        growth = fmax(growth, norm_inf<N>(Xp));
+        if (p == 2 * C) return growth;
+        mm<N>(X, Xp, Xp);
+    }
+}
+template <int N>
 __device__ inline bool all_zero(const double* A) {
     for (int i = 0; i < N * N; i++)
         if (A[i] != 0.0) return false;

@@ -1,0 +1,55 @@
+// stream_tables.h -- the per-latent table blocks of the whole-stream smoother (smoother.hip) and forecasts (forecast.hip), the chunk geometry
+// their chunk powers are built for, and the (d, dtype) dispatch of their launchers.  Read by both files and by capi.cpp.
+#pragma once
+#include "common.h"
+#include <type_traits>
+
+namespace moihgp {
+
+// chunk geometry of the chunk-scan sweeps (scan_sweep.h); MF / MB below are powers for exactly this chunk length
+constexpr int kScanChunk = 16;                  // ticks per lane per segment
+constexpr int kScanSeg = 64 * kScanChunk;       // ticks per segment (one wavefront)
+constexpr int kScanPitch = kScanChunk + 1;      // LDS row pitch of one lane's chunk (odd: no bank conflicts between lanes)
+constexpr int kScanPlane = 64 * kScanPitch;     // elements of one staged plane
+
+// per-latent smoother block (fp64), offsets in doubles
+template <int D>
+struct SM {
+    static constexpr int NN = D * D;
+    static constexpr int A = 0, AKHA = A + NN, K = AKHA + NN, G = K + D;   // AKHA = A - K H A
+    static constexpr int MF = G + NN;           // AKHA^kScanChunk
+    static constexpr int MB = MF + NN;          // G^kScanChunk
+    static constexpr int P = MB + NN, PF = P + NN, PS = PF + NN;
+    static constexpr int VARF = PS + NN, VARS = VARF + 1, GROWTH = VARS + 1, RESID = GROWTH + 1, STATUS = RESID + 1;
+    static constexpr int SIZE = (STATUS + 1 + 1) / 2 * 2;
+};
+
+// per-latent forecast block, offsets in scalars (the same in the fp64 and the fp32 copy)
+template <int D>
+struct FT {
+    static constexpr int NN = D * D;
+    static constexpr int A = 0, M = A + NN, K = M + NN, MF = K + D;   // MF = M^kScanChunk
+    static constexpr int C = MF + NN;                                 // [kFcMaxHorizons][D]  c_k = H A^h_k (rows past the call's K are zero)
+    static constexpr int VAR = C + kFcMaxHorizons * D;                // [kFcMaxHorizons]
+    static constexpr int GROWTH = VAR + kFcMaxHorizons, STATUS = GROWTH + 1;
+    static constexpr int SIZE = (STATUS + 1 + 3) / 4 * 4;
+};
+
+constexpr int sm_size(int d) { return d == 2 ? SM<2>::SIZE : SM<3>::SIZE; }
+constexpr int fc_size(int d) { return d == 2 ? FT<2>::SIZE : FT<3>::SIZE; }
+
+// f(std::integral_constant<int, D>) for the state dimension d (2 or 3); f(Tv(), std::integral_constant<int, D>) for the stream's scalar too
+template <typename F>
+inline void dispatch_dim(int d, F&& f) {
+    if (d == 2) f(std::integral_constant<int, 2>());
+    else f(std::integral_constant<int, 3>());
+}
+template <typename F>
+inline void dispatch_stream(int d, int dtype, F&& f) {
+    dispatch_dim(d, [&](auto dim) {
+        if (dtype == 0) f(double(), dim);
+        else f(float(), dim);
+    });
+}
+
+}  // namespace moihgp

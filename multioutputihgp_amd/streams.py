@@ -308,6 +308,15 @@ class LatentBank:
         _check(rc, self._lib)
         return dict(yhat=yhat, x=x, dx=dx, nll=nll, grad=grad)
 
+    def _start_state(self, Ty: torch.Tensor, x: Optional[torch.Tensor], x_start: Optional[torch.Tensor]):
+        """(x, start) of smooth / forecast: `x` [L, d] receives the end state (zeros if not given), the sweep starts from `x_start` if given, else from `x`."""
+        if x is None:
+            x = torch.zeros((self.L, self.d), dtype=Ty.dtype, device=Ty.device)
+        for name, t in (("x", x), ("x_start", x_start)):
+            if t is not None and (t.dtype != Ty.dtype or not t.is_contiguous() or tuple(t.shape) != (self.L, self.d)):
+                raise ValueError(f"{name} must be a contiguous [L, d] tensor of the stream dtype")
+        return x, (x if x_start is None else x_start)
+
     def smooth(self, Ty: torch.Tensor, T: Optional[int] = None, x: Optional[torch.Tensor] = None, x_start: Optional[torch.Tensor] = None,
                ysmooth: Optional[torch.Tensor] = None, stream=None):
         """Steady-state RTS smoothing of T ticks for every latent (include/moihgp.h moihgp_smooth_stream): the posterior mean at every tick
@@ -319,11 +328,7 @@ class LatentBank:
         T, ld = self._check_stream(Ty, T)
         if self.stacked:
             raise MoihgpError("smooth: stacked models are not supported (Matern-3/2 and -5/2 only)", 3)
-        if x is None:
-            x = torch.zeros((self.L, self.d), dtype=Ty.dtype, device=Ty.device)
-        for name, t in (("x", x), ("x_start", x_start)):
-            if t is not None and (t.dtype != Ty.dtype or not t.is_contiguous() or tuple(t.shape) != (self.L, self.d)):
-                raise ValueError(f"{name} must be a contiguous [L, d] tensor of the stream dtype")
+        x, start = self._start_state(Ty, x, x_start)
         if ysmooth is None:
             ysmooth = alloc_stream(self.L, max(T, 1), Ty.dtype, Ty.device)[:, :T]
         elif (not ysmooth.is_cuda or ysmooth.dtype != Ty.dtype or ysmooth.dim() != 2 or ysmooth.stride(1) != 1 or ysmooth.shape[0] != self.L
@@ -334,7 +339,7 @@ class LatentBank:
         ld_out = ysmooth.stride(0) if self.L > 1 else padded_len(max(T, 1), Ty.dtype)
         status = torch.empty((self.L,), dtype=torch.int32, device=Ty.device)
         rc = self._lib.moihgp_smooth_stream(self._h, _DT[Ty.dtype], C.c_void_p(Ty.data_ptr()), T, ld,
-                                            C.c_void_p((x if x_start is None else x_start).data_ptr()), C.c_void_p(x.data_ptr()),
+                                            C.c_void_p(start.data_ptr()), C.c_void_p(x.data_ptr()),
                                             C.c_void_p(ysmooth.data_ptr()), ld_out, C.c_void_p(status.data_ptr()), _stream_ptr(stream))
         _check(rc, self._lib)
         return ysmooth, x, status
@@ -371,17 +376,13 @@ class LatentBank:
         g = _forecast_gains(gains)
         if self.stacked:
             raise MoihgpError("forecast: stacked models are not supported (Matern-3/2 and -5/2 only)", 3)
-        if x is None:
-            x = torch.zeros((self.L, self.d), dtype=Ty.dtype, device=Ty.device)
-        for name, t in (("x", x), ("x_start", x_start)):
-            if t is not None and (t.dtype != Ty.dtype or not t.is_contiguous() or tuple(t.shape) != (self.L, self.d)):
-                raise ValueError(f"{name} must be a contiguous [L, d] tensor of the stream dtype")
+        x, start = self._start_state(Ty, x, x_start)
         if out is None:
             out = torch.empty((K, self.L, padded_len(max(T, 1), Ty.dtype)), dtype=Ty.dtype, device=Ty.device)[:, :, :T]
         ld_out, plane = _forecast_out_strides(out, K, self.L, T, Ty)
         status = torch.empty((self.L,), dtype=torch.int32, device=Ty.device)
         rc = self._lib.moihgp_forecast_stream(self._h, _DT[Ty.dtype], C.c_void_p(Ty.data_ptr()), T, ld,
-                                              C.c_void_p((x if x_start is None else x_start).data_ptr()), C.c_void_p(x.data_ptr()), hz, K,
+                                              C.c_void_p(start.data_ptr()), C.c_void_p(x.data_ptr()), hz, K,
                                               C.c_void_p(out.data_ptr()), ld_out, plane, g, C.c_void_p(status.data_ptr()), _stream_ptr(stream))
         _check(rc, self._lib)
         return out, x, status
