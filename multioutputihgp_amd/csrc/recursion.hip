@@ -723,8 +723,22 @@ filter_scan_kernel(const T* __restrict__ Ty, size_t Ttot, size_t ld, size_t L, c
 __global__ void __launch_bounds__(1024) nll_total_kernel(const double* __restrict__ nll, size_t L, double* __restrict__ total) {
     __shared__ double red[16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // A thread's terms tid, tid + 1024, ... in batches of kBatch whose loads are all in flight before the first add (the launch follows a
+    // kernel boundary: every load misses, and a loop of dependent load-add iterations pays the misses one after another).  Past the end
+    // the load is clamped to the last entry and +0.0 is added instead, which leaves s as it is (s is never -0.0: it starts from +0.0).
+    constexpr int kBatch = 8;
     double s = 0.0;
-    for (size_t i = tid; i < L; i += 1024) s += nll[i];
+    for (size_t base = 0; base < L; base += (size_t)kBatch * 1024) {
+        double v[kBatch];
+#pragma unroll
+        for (int j = 0; j < kBatch; j++) {
+            const size_t i = base + (size_t)j * 1024 + tid;
+            const double t = nll[i < L ? i : L - 1];
+            v[j] = i < L ? t : 0.0;
+        }
+#pragma unroll
+        for (int j = 0; j < kBatch; j++) s += v[j];
+    }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
     if (lane == 0) red[wave] = s;
@@ -802,7 +816,12 @@ filter_seq_kernel(const T* __restrict__ Ty, size_t Tlen, size_t ld, size_t L, co
 //     DMAs in flight (s_waitcnt vmcnt(0)) before any LDS read it can see.  The waits are counted by hand: vector-memory operations of a
 //     wave complete in issue order, and behind the last piece of segment s there are always exactly NP - 4 younger DMAs and (from
 //     segment 1 on) the 4 stores of segment s - 1.  Pieces past the end of the stream are still issued -- every lane re-reads the last
-//     valid vector, one cache line per instruction -- so that the count holds to the last segment; the ring slots they fill are never read.
+//     valid vector, one cache line per instruction -- so that the count holds to the last segment; the ring slots they fill are never read;
+//   * (round 5) the refill of a segment fetches the whole tile NP / 4 segments ahead from ONE running wave-uniform address (one step of the segment
+//     stride per segment) into ONE LDS base, the four pieces told apart by the instruction's offset, which moves both sides; the results leave
+//     through a second running address.  Only the last NP / 4 refills, whose pieces lie past the end, still compute clamped addresses;
+//   * fp32, D = 3: rows 1 and 2 of every 3 x 3 product (chunk response, scan, replay) are one pair and their multiply-adds v_pk_fma_f32 in the
+//     scalar code's operation order ("packed rows" below) -- bit-identical, 99 fewer vector instructions per full segment (489 -> 390).
 #ifndef MOIHGP_FILTER_DMA
 #define MOIHGP_FILTER_DMA 1
 #endif
@@ -832,6 +851,12 @@ __device__ inline void lds_write4(unsigned a0, unsigned a1, unsigned a2, unsigne
     asm volatile("ds_write_b128 %4, %0\n\tds_write_b128 %5, %1\n\tds_write_b128 %6, %2\n\tds_write_b128 %7, %3"
                  :: "v"(r[0]), "v"(r[1]), "v"(r[2]), "v"(r[3]), "v"(a0), "v"(a1), "v"(a2), "v"(a3) : "memory");
 }
+// the same read at one per-lane address plus 0 / 1 / 2 / 3 KB (four consecutive ring slots)
+template <typename AV>
+__device__ inline void lds_read4_kb(unsigned a, AV (&r)[4]) {
+    asm volatile("ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:1024\n\tds_read_b128 %2, %4 offset:2048\n\tds_read_b128 %3, %4 offset:3072\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&v"(r[0]), "=&v"(r[1]), "=&v"(r[2]), "=&v"(r[3]) : "v"(a) : "memory");
+}
 // N scalars of a wave-uniform table row (16-byte aligned, padded to whole vectors) from LDS: every lane reads the same address (broadcast)
 template <typename T, int N>
 __device__ inline void lds_read_uniform(unsigned addr, T* out) {
@@ -852,6 +877,80 @@ __device__ inline void lds_read_uniform(unsigned addr, T* out) {
     for (int i = 0; i < NV; i++) av_unpack(v[i], &e[i * EPV]);
 #pragma unroll
     for (int i = 0; i < N; i++) out[i] = e[i];
+}
+
+// ---- packed rows (fp32, D = 3) ----------------------------------------------------------------------------------------------------------
+// Rows 1 and 2 of every 3 x 3 product of the segment solve are carried as ONE pair: each of their multiply-adds is then one v_pk_fma_f32
+// (v_pk_mul_f32 for K v) with the scalar operand broadcast, in the operation order of the scalar code -- no result bit changes.  Row 0 and the
+// hx / v chain stay scalar.  A matrix is held as its row 0 and the three column pairs {m[1][j], m[2][j]}.
+template <typename T, int D> constexpr bool kPackRows = sizeof(T) == 4 && D == 3;
+typedef float f2 __attribute__((ext_vector_type(2)));
+__device__ inline f2 pk_fma(f2 a, float b, f2 c) { const f2 bb = {b, b}; return __builtin_elementwise_fma(a, bb, c); }
+struct Mat3Pk { float r[3]; f2 c[3]; };
+__device__ inline Mat3Pk mat3pk(const float* m) {
+    Mat3Pk o;
+#pragma unroll
+    for (int j = 0; j < 3; j++) { o.r[j] = m[j]; o.c[j].x = m[3 + j]; o.c[j].y = m[6 + j]; }
+    return o;
+}
+// matvec_acc<float, 3> on (z0, {z1, z2})
+__device__ inline void matvec_acc_pk(const Mat3Pk& m, const float* t, float& z0, f2& zz) {
+#pragma unroll
+    for (int j = 0; j < 3; j++) z0 = fma(m.r[j], t[j], z0);
+#pragma unroll
+    for (int j = 0; j < 3; j++) zz = pk_fma(m.c[j], t[j], zz);
+}
+// position of entry e of a 3 x 3 table row inside its 12-float LDS row: row 0 first, then the column pairs, each 8-byte aligned
+__device__ inline unsigned pk_row_pos(unsigned e) { return e < 3 ? e : (e < 6 ? 4 + 2 * (e - 3) : 5 + 2 * (e - 6)); }
+__device__ inline Mat3Pk lds_read_mat3pk(unsigned addr) {
+    nt_f4 v0, v1, v2;
+    asm volatile("ds_read_b128 %0, %3\n\tds_read_b128 %1, %3 offset:16\n\tds_read_b128 %2, %3 offset:32\n\ts_waitcnt lgkmcnt(0)"
+                 : "=&v"(v0), "=&v"(v1), "=&v"(v2) : "v"(addr) : "memory");
+    Mat3Pk o;
+    o.r[0] = v0.x; o.r[1] = v0.y; o.r[2] = v0.z;
+    o.c[0] = v1.xy; o.c[1] = v1.zw; o.c[2] = v2.xy;
+    return o;
+}
+template <int CTRL, int ROW_MASK>
+__device__ inline void dpp_level_pk(const Mat3Pk& m, float& z0, f2& zz) {
+    const float t[3] = {dpp0<CTRL, ROW_MASK>(z0), dpp0<CTRL, ROW_MASK>(zz.x), dpp0<CTRL, ROW_MASK>(zz.y)};
+    matvec_acc_pk(m, t, z0, zz);
+}
+template <int SPL>
+__device__ inline void dpp_scan_dma_pk(float& z0, f2& zz, unsigned sp_addr, const Mat3Pk& m1 /* level 0 of the table, already read */, const Mat3Pk& pj) {
+    dpp_level_pk<DPP_ROW_SHR + 1, 0xF>(m1, z0, zz);
+    dpp_level_pk<DPP_ROW_SHR + 2, 0xF>(lds_read_mat3pk(sp_addr + 1 * SPL), z0, zz);
+    dpp_level_pk<DPP_ROW_SHR + 4, 0xF>(lds_read_mat3pk(sp_addr + 2 * SPL), z0, zz);
+    dpp_level_pk<DPP_ROW_SHR + 8, 0xF>(lds_read_mat3pk(sp_addr + 3 * SPL), z0, zz);
+    dpp_level_pk<DPP_ROW_BCAST15, 0x2>(pj, z0, zz);
+    dpp_level_pk<DPP_ROW_BCAST15, 0x4>(pj, z0, zz);
+    dpp_level_pk<DPP_ROW_BCAST15, 0x8>(pj, z0, zz);
+}
+// replay_chunk<float, 3, CK, NLL, TAIL> on the state (x0, {x1, x2})
+template <int CK, bool NLL, bool TAIL>
+__device__ inline void replay_chunk_pk(float* y, float& x0, f2& xx, const Mat3Pk& a, float k0, f2 kk, size_t t0, size_t Tlen, double& acc, unsigned& nobs) {
+    float part = 0;
+#pragma unroll
+    for (int k = 0; k < CK; k++) {
+        const bool valid = !TAIL || (t0 + k) < Tlen;
+        float hx = 0;
+        hx = fma(a.r[0], x0, hx); hx = fma(a.r[1], xx.x, hx); hx = fma(a.r[2], xx.y, hx);
+        float v = y[k] - hx;
+        if (TAIL) v = valid ? v : 0.f;
+        if (NLL) {
+            part = fma(v, v, part);
+            if (TAIL) nobs += valid ? 1u : 0u;
+        }
+        const float xn0 = fma(k0, v, hx);
+        const f2 vv = {v, v};
+        f2 ss = kk * vv;
+        ss = pk_fma(a.c[0], x0, ss); ss = pk_fma(a.c[1], xx.x, ss); ss = pk_fma(a.c[2], xx.y, ss);
+        x0 = (TAIL && !valid) ? x0 : xn0;
+        xx.x = (TAIL && !valid) ? xx.x : ss.x;
+        xx.y = (TAIL && !valid) ? xx.y : ss.y;
+        y[k] = x0;
+    }
+    if (NLL) acc += (double)part;
 }
 
 // dpp_scan (kernels_common.h) with the in-row powers M^(1,2,4,8) fetched from the wave's LDS table by the reads above
@@ -897,6 +996,42 @@ struct DmaConst {
 // are valid or not: no per-tick mask, lanes past the end hold zeros and are simply not counted); 2 = ragged, any length (replay masked per tick)
 template <typename T, int D, int CK, int SPL, bool NLL, int TAIL>
 __device__ inline bool dma_segment(T* y, T* xin, const DmaConst<T, D, CK>& c, int lane, size_t t0, size_t Tlen, double& acc, unsigned& nobs) {
+    if constexpr (kPackRows<T, D>) {
+        float z0 = 0.f;
+        f2 zz = {0.f, 0.f};
+#pragma unroll
+        for (int k = 0; k < CK; k++) {
+            z0 = fma(c.g[k * 3], y[k], z0);
+            const f2 gg = {c.g[k * 3 + 1], c.g[k * 3 + 2]};
+            zz = pk_fma(gg, y[k], zz);
+        }
+        if (__any((z0 != z0) | (zz.x != zz.x) | (zz.y != zz.y))) return false;
+        const Mat3Pk m1 = lds_read_mat3pk(c.sp_addr);                  // M = M^1 (level 0 of the table): lane 0's start term and the first scan level
+        {
+            const float x0[3] = {(lane == 0) ? xin[0] : 0.f, (lane == 0) ? xin[1] : 0.f, (lane == 0) ? xin[2] : 0.f};
+            matvec_acc_pk(m1, x0, z0, zz);
+        }
+        const Mat3Pk pj = mat3pk(c.pj), a = mat3pk(c.a);
+        dpp_scan_dma_pk<SPL>(z0, zz, c.sp_addr, m1, pj);
+        float xs0 = wave_shr1(z0, xin[0]);
+        f2 xx = {wave_shr1(zz.x, xin[1]), wave_shr1(zz.y, xin[2])};
+        const f2 kk = {c.k[1], c.k[2]};
+        int jl = 63;
+        if (TAIL == 1) {
+            double part = 0.0; unsigned none = 0;
+            replay_chunk_pk<CK, NLL, false>(y, xs0, xx, a, c.k[0], kk, t0, Tlen, part, none);
+            const bool valid = t0 < Tlen;
+            if (NLL) { acc += valid ? part : 0.0; nobs += valid ? (unsigned)CK : 0u; }
+            jl = (int)((Tlen - 1 - (t0 - (size_t)lane * CK)) / CK);
+        } else if (TAIL == 2) {
+            replay_chunk_pk<CK, NLL, true>(y, xs0, xx, a, c.k[0], kk, t0, Tlen, acc, nobs);
+            jl = (int)((Tlen - 1 - (t0 - (size_t)lane * CK)) / CK);
+        } else {
+            replay_chunk_pk<CK, NLL, false>(y, xs0, xx, a, c.k[0], kk, t0, Tlen, acc, nobs);
+        }
+        xin[0] = read_lane(xs0, jl); xin[1] = read_lane(xx.x, jl); xin[2] = read_lane(xx.y, jl);
+        return true;
+    }
     T z[D];
 #pragma unroll
     for (int i = 0; i < D; i++) z[i] = T(0);
@@ -982,7 +1117,7 @@ filter_dma_kernel(const T* __restrict__ Ty, size_t Tlen, size_t ld, size_t L, co
         }
         return;
     }
-    // ---- the stream first: prologue, the whole ring -----------------------------------------------------------------------------------
+    // ---- addresses of the stream -----------------------------------------------------------------------------------
     const size_t nseg = (Tlen + SEG - 1) / SEG;
     const size_t nfullp = Tlen / PT;                           // pieces that lie entirely inside the stream
     const unsigned jj = lane & 15, rr = lane >> 4;
@@ -1008,21 +1143,8 @@ filter_dma_kernel(const T* __restrict__ Ty, size_t Tlen, size_t ld, size_t L, co
             __builtin_amdgcn_global_load_lds((glb_cvoid_t*)(rowb + o), dst, 16, 0, 0);
         }
     };
-    if (nfullp >= (size_t)NP) {
-#pragma unroll
-        for (int i = 0; i < NP; i++) issue_piece((size_t)i, (unsigned)i, true);
-    } else {
-#pragma unroll
-        for (int i = 0; i < NP; i++) issue_piece((size_t)i, (unsigned)i, false);
-    }
-    // ---- per-lane constants: plain loads, issued behind the ring.  The compiler waits for them with vmcnt(0) at their first use (it does
-    // not count past LDS-DMA operations): once per sweep, inside segment 0, which needs the head of the ring anyway ------------------------
-    DmaConst<T, D, CK> c;
-#pragma unroll
-    for (int i = 0; i < D * D; i++) c.pj[i] = cb[Lay::PJ + (lane & 15) * D * D + i];
-    const T spv = cb[Lay::SP + (lane < 4 * D * D ? lane : 0)];   // lane e < 4 D D: entry e of the power table, on its way to LDS
-
     // ---- wave-uniform constants (scalar loads: their own counter) -------------------------------------------------------------------
+    DmaConst<T, D, CK> c;
 #pragma unroll
     for (int i = 0; i < D * D; i++) c.a[i] = cb[Lay::A + i];
 #pragma unroll
@@ -1034,32 +1156,55 @@ filter_dma_kernel(const T* __restrict__ Ty, size_t Tlen, size_t ld, size_t L, co
     T xin[D];
 #pragma unroll
     for (int i = 0; i < D; i++) xin[i] = xin0[l * D + i];
+    // ---- the stream: prologue, the whole ring ---------------------------------------------------------------------------------------
+    if (nfullp >= (size_t)NP) {
+#pragma unroll
+        for (int i = 0; i < NP; i++) issue_piece((size_t)i, (unsigned)i, true);
+    } else {
+#pragma unroll
+        for (int i = 0; i < NP; i++) issue_piece((size_t)i, (unsigned)i, false);
+    }
+    // ---- per-lane constants: plain loads, issued behind the ring.  The compiler waits for them with vmcnt(0) at their first use (it does
+    // not count past LDS-DMA operations): once per sweep, ahead of segment 0.  (Fetching them ahead of the ring by inline-asm loads, so that
+    // segment 0 really starts at vmcnt(NP - 4), was built and measured in round 5: no gain) ----------------------------
+#pragma unroll
+    for (int i = 0; i < D * D; i++) c.pj[i] = cb[Lay::PJ + (lane & 15) * D * D + i];
+    const T spv = cb[Lay::SP + (lane < 4 * D * D ? lane : 0)];   // lane e < 4 D D: entry e of the power table, on its way to LDS
+
     double acc = 0.0;
     unsigned nobs = 0;
     size_t nobs_uniform = 0;
     unsigned char* orowb = WRITE ? (TILED ? reinterpret_cast<unsigned char*>(yhat) + l * 4096 : reinterpret_cast<unsigned char*>(yhat + l * ldo)) : nullptr;
 
+    // ---- segment 0 needs its own four pieces (in effect the whole ring: see the per-lane constants above) ---------------------------
+    wait_vmcnt<NP - 4>();
+    // power table -> LDS, level lv at sp_addr + lv SPL
+    if (lane < 4 * D * D) {
+        unsigned e = (unsigned)(lane % (D * D));
+        if constexpr (kPackRows<T, D>) e = pk_row_pos(e);      // (rows 1 and 2 interleaved: the scan reads them as column pairs)
+        const unsigned a = sp_addr + (unsigned)(lane / (D * D)) * SPL + e * (unsigned)sizeof(T);
+        if constexpr (sizeof(T) == 4) asm volatile("ds_write_b32 %0, %1" :: "v"(a), "v"(spv) : "memory");
+        else asm volatile("ds_write_b64 %0, %1" :: "v"(a), "v"(spv) : "memory");
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+
+    // Running addresses, one step of seg_stride per segment: the tile the refill of this segment fetches (NP / 4 segments ahead) and the tile
+    // its results go to, both wave-uniform (the lane's share is goff)
+    constexpr bool RING4 = NP % 4 == 0;                        // a segment's four slots are consecutive: slot0, +1, +2, +3, no wrap
+    const size_t nin = TILED ? nseg : nfullp / 4;              // segments whose four pieces are fetched unclamped
+    const unsigned char* inb = rowb + (size_t)(NP / 4) * seg_stride;
+    unsigned char* outb = orowb;
+    // An unstable latent (rho(AKHA) > 1: scan tables overflowed, flagged by IHGP::update) is left to filter_seq_kernel
+    const size_t nsweep = scanok == T(0) ? 0 : nseg;
     unsigned slot0 = 0;
-    for (size_t seg = 0; seg < nseg; seg++) {
+    for (size_t seg = 0; seg < nsweep; seg++) {
         // ---- wait for this segment's four pieces ------------------------------------------------------------------------------------
-        if (seg == 0) {
-            wait_vmcnt<NP - 4>();
-            // power table -> LDS, level lv at sp_addr + lv SPL
-            if (lane < 4 * D * D) {
-                const unsigned a = sp_addr + (unsigned)(lane / (D * D)) * SPL + (unsigned)(lane % (D * D)) * (unsigned)sizeof(T);
-                if constexpr (sizeof(T) == 4) asm volatile("ds_write_b32 %0, %1" :: "v"(a), "v"(spv) : "memory");
-                else asm volatile("ds_write_b64 %0, %1" :: "v"(a), "v"(spv) : "memory");
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            // An unstable latent (rho(AKHA) > 1: scan tables overflowed, flagged by IHGP::update) is left to filter_seq_kernel
-            if (scanok == T(0)) break;
-        } else {
-            wait_vmcnt<WSTEADY>();
-        }
+        if (seg > 0) wait_vmcnt<WSTEADY>();
         const size_t tbase = seg * SEG;
         const size_t t0 = tbase + (size_t)lane * CK;
         // this lane's 64 bytes: row rr of the segment = piece 4 seg + rr, in slot (slot0 + rr) mod NP
-        unsigned sl = slot0 + rr; sl = sl >= (unsigned)NP ? sl - NP : sl;
+        unsigned sl = slot0 + rr;
+        if constexpr (!RING4) sl = sl >= (unsigned)NP ? sl - NP : sl;
         const unsigned cbase = ring_addr + sl * 1024 + jj * 64;
         const unsigned ca0 = cbase + (sw << 4), ca1 = cbase + ((sw ^ 1u) << 4), ca2 = cbase + ((sw ^ 2u) << 4), ca3 = cbase + ((sw ^ 3u) << 4);   // vector k at 16 (k ^ sw)
         bool done;
@@ -1109,8 +1254,9 @@ filter_dma_kernel(const T* __restrict__ Ty, size_t Tlen, size_t ld, size_t L, co
         if (WRITE) {
             AV o[4];
             const unsigned la = ring_addr + (unsigned)lane * 16;
-            lds_read4<AV>(la + slot0 * 1024, la + s1 * 1024, la + s2 * 1024, la + s3 * 1024, o);
-            unsigned char* po = orowb + seg * seg_stride + goff;
+            if constexpr (RING4) lds_read4_kb<AV>(la + slot0 * 1024, o);
+            else lds_read4<AV>(la + slot0 * 1024, la + s1 * 1024, la + s2 * 1024, la + s3 * 1024, o);
+            unsigned char* po = outb + goff;
             if (TILED || tbase + SEG <= Tlen) {                  // (a tile is stored whole: its padding belongs to the stream)
 #pragma unroll
                 for (int i = 0; i < 4; i++) __builtin_nontemporal_store(o[i], reinterpret_cast<AV*>(po + i * 1024));
@@ -1123,10 +1269,20 @@ filter_dma_kernel(const T* __restrict__ Ty, size_t Tlen, size_t ld, size_t L, co
         // ---- refill the four slots with the pieces NP ahead (only while another segment will wait on the count) ---------------------
         if (seg + 1 < nseg) {
             const size_t pn = 4 * seg + NP;
-            if (pn + 4 <= nfullp) { issue_piece(pn + 0, slot0, true); issue_piece(pn + 1, s1, true); issue_piece(pn + 2, s2, true); issue_piece(pn + 3, s3, true); }
+            if (RING4 && seg + NP / 4 < nin) {
+                // the whole tile NP / 4 segments ahead: one address and one LDS base, the pieces by the instruction's offset (it moves both sides)
+                glb_cvoid_t* src = (glb_cvoid_t*)(inb + goff);
+                lds_void_t* dst = (lds_void_t*)(ring + (size_t)slot0 * 1024);
+                __builtin_amdgcn_global_load_lds(src, dst, 16, 0, 0);
+                __builtin_amdgcn_global_load_lds(src, dst, 16, 1024, 0);
+                __builtin_amdgcn_global_load_lds(src, dst, 16, 2048, 0);
+                __builtin_amdgcn_global_load_lds(src, dst, 16, 3072, 0);
+            } else if (pn + 4 <= nfullp) { issue_piece(pn + 0, slot0, true); issue_piece(pn + 1, s1, true); issue_piece(pn + 2, s2, true); issue_piece(pn + 3, s3, true); }
             else { issue_piece(pn + 0, slot0, false); issue_piece(pn + 1, s1, false); issue_piece(pn + 2, s2, false); issue_piece(pn + 3, s3, false); }
         }
         slot0 += 4; slot0 = slot0 >= (unsigned)NP ? slot0 - NP : slot0;
+        inb += seg_stride;
+        if (WRITE) outb += seg_stride;
     }
     wait_vmcnt<0>();                                           // no DMA may land in LDS that the next workgroup already owns
 
