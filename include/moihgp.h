@@ -151,7 +151,7 @@ int         moihgp_get_latent(moihgp_gp* gp, size_t l, double* A, double* K, dou
                               double* dA, double* dS, double* dK, double* dAKHA, double* HdA, int* iters);
 
 /* ---- ordering contract of the batched entries ---------------------------------------------------
- * moihgp_filter_stream(_io), moihgp_grad_stream, moihgp_project_stream and moihgp_unproject_stream are ASYNCHRONOUS on the
+ * moihgp_filter_stream(_io), moihgp_grad_stream, moihgp_project_stream and moihgp_unproject_stream (and their _tiled forms) are ASYNCHRONOUS on the
  * stream the caller passes and read the handle's per-latent tables and mixing.  gpXX_update, moihgp_update_latents,
  * moihgp_set_mixing and moihgp_reseed_U rewrite those; they (a) first make their internal stream wait for everything enqueued so
  * far on every stream that carried batched work of this handle, so a rewrite never overtakes a sweep that is still in flight,
@@ -231,7 +231,8 @@ int moihgp_filter_stream_v2(moihgp_gp* gp, int dtype, const void* Ty, size_t T, 
  * input and unspecified on output).  The wavefronts of a launch move through the segments together, so the chip reads and writes one
  * contiguous front instead of L row streams: a cold stream moves ~12 % faster.  For the reference's own models (d = 2, 3);
  * stacked models return 3.  x_in / x / nll / nll_total / stream as moihgp_filter_stream_io; yhat (may be NULL) in the same layout.
- * moihgp_stream_retile copies between the two layouts (to_tiled != 0: src series-major with row stride ld, dst segment-major). */
+ * moihgp_stream_retile copies between the two layouts (to_tiled != 0: src series-major with row stride ld, dst segment-major); a stream that
+ * comes from observations and goes back to outputs needs no such copy: moihgp_project_stream_tiled / moihgp_unproject_stream_tiled below. */
 int moihgp_filter_stream_tiled(moihgp_gp* gp, int dtype, const void* Ty_tiled, size_t T, const void* x_in, void* x, void* yhat_tiled, double* nll,
                                double* nll_total, void* stream);
 int moihgp_stream_retile(int dtype, const void* src, void* dst, size_t L, size_t T, size_t ld, int to_tiled, void* stream);
@@ -335,6 +336,18 @@ int moihgp_project_stream(moihgp_gp* gp, int dtype, const void* Y, size_t T, voi
 int moihgp_ls_shard_gram(moihgp_gp* gp, int dtype, const void* Y, const int* ticks, size_t n, int kmax, const void* Ty, size_t ld, double* packed, void* stream);
 int moihgp_ls_shard_apply(moihgp_gp* gp, int dtype, const void* Y, const int* ticks, size_t n, int kmax, const double* packed, void* Ty, size_t ld, void* stream);
 int moihgp_unproject_stream(moihgp_gp* gp, int dtype, const void* Tyhat, size_t T, size_t ld, void* Yhat, void* stream);
+/* The same two products with the stream in the SEGMENT-MAJOR layout of moihgp_filter_stream_tiled ("segment-major streams" above:
+ * [ceil(T / SEG)][L][SEG], tile (s, l) at ((s L + l) SEG) scalars from the base, the last tile allocated whole), so that
+ *     Y [T][M]  ->  moihgp_project_stream_tiled  ->  moihgp_filter_stream_tiled  ->  moihgp_unproject_stream_tiled  ->  Yhat [T][M]
+ * runs without a moihgp_stream_retile pass on either side.  The arithmetic, its order and the results are those of the series-major entries
+ * bit for bit; only the addresses differ.  Everything else is theirs too: a full object, asynchronous on `stream` under the ordering contract,
+ * the least-squares projection of ticks with missing outputs with the same limits (beyond them the tick's NaN column stands).
+ * Ticks past T in the last tile: UNSPECIFIED after the projection (it never writes them -- whatever the buffer held stays), IGNORED by the
+ * un-projection (it never reads them: they may hold NaN).  The projection applies to stacked models as well; their sweep takes series-major
+ * streams only.  Returns 1 for an unknown dtype, a null pointer or a segment-major base that is not 16-byte aligned (T > 0); T == 0 returns 0
+ * and touches nothing. */
+int moihgp_project_stream_tiled(moihgp_gp* gp, int dtype, const void* Y, size_t T, void* Ty_tiled, void* stream);
+int moihgp_unproject_stream_tiled(moihgp_gp* gp, int dtype, const void* Tyhat_tiled, size_t T, void* Yhat, void* stream);
 
 /* ---- the learners' windowed objective as one call (HOST pointers, fp64) -----------------------------
  * One evaluation of the loop of moihgp_online.h:61-70 / moihgp_regression.h:42-50 / online_learning.py:83-89:

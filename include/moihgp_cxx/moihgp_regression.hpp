@@ -188,6 +188,47 @@ public:
         for (size_t t = 0; t < T; t++) for (size_t m = 0; m < M; m++) Yf[t][m] = flat[t * M + m];
         return Yf;
     }
+    // (not in the reference) predict() as ONE pass over the whole series on the device (include/moihgp.h): project -> filter -> un-project in
+    // fp64 from a zero start state, where predict() makes one gp32_step3 round trip per tick; element t is what predict() returns at tick t, to
+    // rounding.  tiled = true runs the segment-major entries (moihgp_project_stream_tiled -> moihgp_filter_stream_tiled ->
+    // moihgp_unproject_stream_tiled: the layout of the many-latent sweep, no copy between layouts); tiled = false the series-major ones.  The
+    // two agree bit for bit above 1024 latents and to rounding below (there the series-major sweep splits a stream over wavefronts).
+    // Limits against predict(): missing outputs (NaN) go through moihgp_project_stream's least-squares projection -- a tick with more than 64
+    // missing outputs, or fewer than num_latent observed ones, is treated as missing as a whole (the filter predicts across it), where predict()
+    // projects any tick with at least one observed output.  Stacked models refuse tiled = true (std::runtime_error, the library's return
+    // code 3): their sweep takes series-major streams only.
+    std::vector<Vector> predictStream(const std::vector<Vector>& Y, bool tiled = false) {
+        const size_t T = Y.size(), M = _num_output, L = _num_latent, seg = 512 /* fp64 ticks per tile */;
+        const size_t ld = (T + 1) / 2 * 2, n = tiled ? (T + seg - 1) / seg * L * seg : L * ld;
+        std::vector<Vector> Yhat(T, Vector(M, 0.0));
+        if (T == 0) return Yhat;
+        Vector flat(T * M), zeros(L * _dim, 0.0);
+        for (size_t t = 0; t < T; t++) for (size_t m = 0; m < M; m++) flat[t * M + m] = Y[t][m];
+        moihgp_dvec_ctx* ctx = moihgp_dvec_ctx_new();
+        double *dY = moihgp_dvec_alloc(T * M), *dTy = moihgp_dvec_alloc(n), *dyh = moihgp_dvec_alloc(n), *dx = moihgp_dvec_alloc(L * _dim);
+        int rc = (ctx && dY && dTy && dyh && dx) ? 0 : 4;
+        void* s = ctx ? moihgp_dvec_ctx_stream(ctx) : nullptr;
+        moihgp_gp* h = _moihgp->handle();
+        if (!rc) rc = moihgp_dvec_upload(ctx, dY, flat.data(), T * M);
+        if (!rc) rc = moihgp_dvec_upload(ctx, dx, zeros.data(), L * _dim);
+        if (tiled) {
+            if (!rc) rc = moihgp_project_stream_tiled(h, MOIHGP_F64, dY, T, dTy, s);
+            if (!rc) rc = moihgp_filter_stream_tiled(h, MOIHGP_F64, dTy, T, dx, dx, dyh, nullptr, nullptr, s);
+            if (!rc) rc = moihgp_unproject_stream_tiled(h, MOIHGP_F64, dyh, T, dY, s);
+        } else {
+            if (!rc) rc = moihgp_project_stream(h, MOIHGP_F64, dY, T, dTy, ld, s);
+            if (!rc) rc = moihgp_filter_stream_v2(h, MOIHGP_F64, dTy, T, ld, dx, dx, dyh, ld, nullptr, nullptr, s);
+            if (!rc) rc = moihgp_unproject_stream(h, MOIHGP_F64, dyh, T, ld, dY, s);
+        }
+        if (!rc) rc = moihgp_dvec_download(ctx, flat.data(), dY, T * M);
+        const std::string err = rc ? moihgp_last_error() : "";
+        if (ctx) { moihgp_dvec_sync(ctx); moihgp_release_stream(h, s); }
+        for (double* p : {dY, dTy, dyh, dx}) if (p) moihgp_dvec_free(p);
+        if (ctx) moihgp_dvec_ctx_del(ctx);
+        if (rc) throw std::runtime_error("predictStream: " + err);
+        for (size_t t = 0; t < T; t++) for (size_t m = 0; m < M; m++) Yhat[t][m] = flat[t * M + m];
+        return Yhat;
+    }
     Vector getParams() { return _moihgp->getParams(); }
     size_t getNumParam() { return _num_param; }
     size_t getNumOutput() { return _num_output; }

@@ -1258,6 +1258,44 @@ static int unproject_stream_impl(moihgp_gp* gp, int dtype, const void* Tyhat, si
                                    (hipStream_t)stream);
 }
 
+// segment-major streams straight out of the projection and into the un-projection (include/moihgp.h: moihgp_project_stream_tiled)
+static int check_tiled_product_args(moihgp_gp* gp, const char* what, int dtype, const void* dense, const void* tiled, size_t T) {
+    if (!gp || gp->latents_only) { set_last_error("%s needs a full MOIHGP object", what); return 1; }
+    if (dtype != MOIHGP_F64 && dtype != MOIHGP_F32) { set_last_error("dtype must be MOIHGP_F64 or MOIHGP_F32"); return 1; }
+    if (T == 0) return 0;
+    if (!dense || !tiled) { set_last_error("%s: null stream pointer", what); return 1; }
+    if (((uintptr_t)tiled & 15) != 0) { set_last_error("%s: the segment-major stream's base must be 16-byte aligned", what); return 1; }
+    return 0;
+}
+
+static int project_stream_tiled_impl(moihgp_gp* gp, int dtype, const void* Y, size_t T, void* Ty, void* stream) {
+    if (int rc = check_tiled_product_args(gp, "project_stream_tiled", dtype, Y, Ty, T)) return rc;
+    if (T == 0) return 0;
+    note_user_stream(gp, (hipStream_t)stream);
+    if (int rc = launch_project_stream(dtype, Y, T, gp->M, gp->L, gp->dU, dtype == MOIHGP_F64 ? nullptr : mixing_f32(gp), gp->dinvsqrtS, Ty, 0,
+                                       (hipStream_t)stream, true)) return rc;
+    // partially observed ticks, exactly as project_stream_impl: the same kernel with the tiled address of the tick's column
+    if (gp->mix_ortho && ls_project_fits(gp->L))
+        return launch_project_stream_missing(dtype, Y, T, gp->M, gp->L, gp->dU, gp->dinvsqrtS, Ty, 0, (hipStream_t)stream, true);
+    return 0;
+}
+
+int moihgp_project_stream_tiled(moihgp_gp* gp, int dtype, const void* Y, size_t T, void* Ty_tiled, void* stream) {
+    return guard_rc([&] { return project_stream_tiled_impl(gp, dtype, Y, T, Ty_tiled, stream); });
+}
+
+static int unproject_stream_tiled_impl(moihgp_gp* gp, int dtype, const void* Tyhat, size_t T, void* Yhat, void* stream) {
+    if (int rc = check_tiled_product_args(gp, "unproject_stream_tiled", dtype, Yhat, Tyhat, T)) return rc;
+    if (T == 0) return 0;
+    note_user_stream(gp, (hipStream_t)stream);
+    return launch_unproject_stream(dtype, Tyhat, T, 0, gp->M, gp->L, gp->dU, dtype == MOIHGP_F64 ? nullptr : mixing_f32(gp), gp->dsqrtS, Yhat,
+                                   (hipStream_t)stream, true);
+}
+
+int moihgp_unproject_stream_tiled(moihgp_gp* gp, int dtype, const void* Tyhat_tiled, size_t T, void* Yhat, void* stream) {
+    return guard_rc([&] { return unproject_stream_tiled_impl(gp, dtype, Tyhat_tiled, T, Yhat, stream); });
+}
+
 // Latent shards: the two halves of the least-squares projection of partially observed ticks around the caller's all-reduce (tick.hip)
 int moihgp_ls_shard_gram(moihgp_gp* gp, int dtype, const void* Y, const int* ticks, size_t n, int kmax, const void* Ty, size_t ld, double* packed, void* stream) {
     return guard_rc([&] {

@@ -252,8 +252,9 @@ constexpr int kLsMaxMissing = 64;          // missing outputs per tick the k x k
 // the least-squares kernel keeps r = U^T y0 [L] and the augmented k x (k + 1) system in the workgroup's LDS: L <= 15040
 constexpr size_t ls_project_lds_bytes(size_t L) { return (L + (size_t)kLsMaxMissing * (kLsMaxMissing + 1)) * sizeof(double); }
 constexpr bool ls_project_fits(size_t L) { return ls_project_lds_bytes(L) <= 150 * 1024; }
+// tiled: Ty is segment-major [ceil(T / SEG)][L][SEG] (ld unused)
 int launch_project_stream_missing(int dtype, const void* Y, size_t T, size_t M, size_t L, const double* U, const double* invsqrtS, void* Ty, size_t ld,
-                                   hipStream_t s);
+                                   hipStream_t s, bool tiled = false);
 // the same with the latents split over ranks: phase 0 = this rank's part of [U_miss r | U_miss U_miss^T] per affected tick (packed [n][kmax + kmax^2]),
 // phase 1 = solve the (all-reduced) k x k systems and correct this rank's rows of Ty.  ticks: device int32 [n], the affected ticks.
 int launch_ls_shard(int phase, int dtype, const void* Y, size_t M, size_t Lr, const int* ticks, size_t n, int kmax, const double* U, const double* sqrtS,
@@ -279,9 +280,9 @@ void launch_nll_tick(const TickArgs& a, const double* x, const double* y, const 
 void launch_scales(const double* S, size_t L, double* sqrtS, double* invsqrtS, hipStream_t s);
 void launch_narrow(const double* src, size_t n, float* dst, hipStream_t s);       // dst = (float) src
 int launch_project_stream(int dtype, const void* Y, size_t T, size_t M, size_t L, const double* U, const float* U32 /* optional fp32 image of U */, const double* invsqrtS,
-                          void* Ty, size_t ld, hipStream_t s);
+                          void* Ty, size_t ld, hipStream_t s, bool tiled = false /* Ty segment-major [ceil(T / SEG)][L][SEG], ld unused */);
 int launch_unproject_stream(int dtype, const void* Tyhat, size_t T, size_t ld, size_t M, size_t L, const double* U, const float* U32,
-                            const double* sqrtS, void* Yhat, hipStream_t s);
+                            const double* sqrtS, void* Yhat, hipStream_t s, bool tiled = false /* Tyhat segment-major, ld unused */);
 // gradU[r][c] = sum_t Y[t][r] Z[c][t]   (Y tick-major [W][M], Z series-major [L][ldz])
 int launch_ugrad_gemm(const double* Y, size_t W, size_t M, const double* Z, size_t ldz, size_t L, double* gradU, hipStream_t s);
 int launch_gram(const double* X, size_t M, size_t L, double* G, hipStream_t s);                       // G = X^T X

@@ -10,6 +10,13 @@
 //   C(i,j) = C[i*ldc + j]
 // so every product needed here runs without a transpose pass.
 //
+// Segment-major streams (include/moihgp.h: [ceil(T / SEG)][L][SEG], SEG = 4096 / sizeof(scalar) ticks) -- template parameter SEGM:
+//   SEGM_C: C is such a stream with i = latent, j = tick (the projection writes the tiled sweep's input);
+//   SEGM_A: A (i-contiguous) is one with i = tick, k = latent (the un-projection reads the tiled sweep's output).
+// SEG is a multiple of the 128-wide tile, so a tile lies in ONE segment s, where element (latent l, tick t) sits at
+// (s L + l) SEG + (t - s SEG) = s SEG (L - 1) + l SEG + t: the series-major address with leading dimension SEG from a base moved by
+// s SEG (L - 1).  A workgroup moves its base and swaps its leading dimension once, before the first fetch; the loops are the same code.
+//
 // Tile: 128 x 128 x 16 per 256-thread workgroup; 4 waves as 2 x 2, each wave 64 x 64 = 4 x 4 MFMA tiles of
 // 16 x 16 (v_mfma_f64_16x16x4_f64 / v_mfma_f32_16x16x4_f32: one element of A and of B per lane per
 // instruction).  Both operands are staged k-major in LDS (As[k][i], Bs[k][j], row stride 128 + 16 elements so that
@@ -64,9 +71,11 @@ template <> __device__ inline void load8<float, float>(const float* p, float* o)
     for (int v = 0; v < 2; v++) { float4 t = q[v]; o[4 * v] = t.x; o[4 * v + 1] = t.y; o[4 * v + 2] = t.z; o[4 * v + 3] = t.w; }
 }
 
+enum { SEGM_NONE = 0, SEGM_C = 1, SEGM_A = 2 };
+
 // SYM: the product is symmetric (Gram matrix X^T X): only tiles on or above the diagonal are computed; mirror_upper_kernel
 // fills the lower triangle afterwards with coalesced reads and writes.
-template <typename TC, typename TA, typename TB, bool A_ICONTIG, bool B_KCONTIG, bool SYM = false>
+template <typename TC, typename TA, typename TB, bool A_ICONTIG, bool B_KCONTIG, bool SYM = false, int SEGM = SEGM_NONE>
 __global__ void __launch_bounds__(256)
 gemm_mfma_kernel(size_t Mi, size_t Nj, size_t Kk, const TA* __restrict__ A, size_t lda, const TB* __restrict__ B, size_t ldb,
                  TC* __restrict__ C, size_t ldc, const double* __restrict__ rs, int rs_mode, const double* __restrict__ ks, int ks_mode,
@@ -111,6 +120,20 @@ gemm_mfma_kernel(size_t Mi, size_t Nj, size_t Kk, const TA* __restrict__ A, size
         tn = (bid % per_group) / gsz;
     }
     const size_t i0 = (size_t)tm * BM, j0 = (size_t)tn * BN;
+    // segment-major operand: this tile's segment as a base and a leading dimension (lda / ldc as passed are not read); the bounds stay
+    // those of the stream -- ticks past its end in the last tile are neither stored (gj < Nj) nor fetched (gi < Mi, i_full)
+    if constexpr (SEGM == SEGM_C) {
+        static_assert(!SYM && (4096 / sizeof(TC)) % BN == 0, "a column tile must not straddle a segment");
+        constexpr size_t SEG = 4096 / sizeof(TC);
+        C += (j0 / SEG) * SEG * (Mi - 1);
+        ldc = SEG;
+    }
+    if constexpr (SEGM == SEGM_A) {
+        static_assert(!SYM && A_ICONTIG && (4096 / sizeof(TA)) % BM == 0, "a row tile must not straddle a segment");
+        constexpr size_t SEG = 4096 / sizeof(TA);
+        A += (i0 / SEG) * SEG * (Kk - 1);
+        lda = SEG;
+    }
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
@@ -301,12 +324,12 @@ __global__ void __launch_bounds__(256) mirror_upper_kernel(double* __restrict__ 
         }
 }
 
-template <typename TC, typename TA, typename TB, bool AI, bool BK_, bool SYM = false>
+template <typename TC, typename TA, typename TB, bool AI, bool BK_, bool SYM = false, int SEGM = SEGM_NONE>
 int launch(size_t Mi, size_t Nj, size_t Kk, const TA* A, size_t lda, const TB* B, size_t ldb, TC* C, size_t ldc, const double* rs,
            int rs_mode, const double* ks, int ks_mode, hipStream_t s) {
     const unsigned tm = (unsigned)((Mi + BM - 1) / BM), tn = (unsigned)((Nj + BN - 1) / BN);
     if (tm == 0 || tn == 0) return 0;
-    hipLaunchKernelGGL((gemm_mfma_kernel<TC, TA, TB, AI, BK_, SYM>), dim3(SYM ? tm * (tm + 1) / 2 : tm * tn), dim3(256), 0, s, Mi, Nj, Kk, A, lda, B, ldb, C, ldc, rs,
+    hipLaunchKernelGGL((gemm_mfma_kernel<TC, TA, TB, AI, BK_, SYM, SEGM>), dim3(SYM ? tm * (tm + 1) / 2 : tm * tn), dim3(256), 0, s, Mi, Nj, Kk, A, lda, B, ldb, C, ldc, rs,
                        rs_mode, ks, ks_mode, tm, tn);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_last_error("gemm_mfma launch: %s", hipGetErrorString(e)); return 2; }
@@ -336,7 +359,12 @@ void launch_narrow(const double* src, size_t n, float* dst, hipStream_t s) {
 }
 // Ty[l][t] = S_l^-1/2 * sum_m U[m][l] Y[t][m]:  i = l, j = t, k = m;  A = U (i-contiguous, lda = L);  B = Y (k-contiguous, ldb = M)
 int launch_project_stream(int dtype, const void* Y, size_t T, size_t M, size_t L, const double* U, const float* U32, const double* S /* invsqrtS */,
-                          void* Ty, size_t ld, hipStream_t s) {
+                          void* Ty, size_t ld, hipStream_t s, bool tiled) {
+    if (tiled) {      // Ty segment-major (ld unused): the same three kernels with the tiled C store
+        if (dtype == 0) return launch<double, double, double, true, true, false, SEGM_C>(L, T, M, U, L, (const double*)Y, M, (double*)Ty, 0, S, 1, nullptr, 0, s);
+        if (U32) return launch<float, float, float, true, true, false, SEGM_C>(L, T, M, U32, L, (const float*)Y, M, (float*)Ty, 0, S, 1, nullptr, 0, s);
+        return launch<float, double, float, true, true, false, SEGM_C>(L, T, M, U, L, (const float*)Y, M, (float*)Ty, 0, S, 1, nullptr, 0, s);
+    }
     if (dtype == 0) return launch<double, double, double, true, true>(L, T, M, U, L, (const double*)Y, M, (double*)Ty, ld, S, 1, nullptr, 0, s);
     if (U32) return launch<float, float, float, true, true>(L, T, M, U32, L, (const float*)Y, M, (float*)Ty, ld, S, 1, nullptr, 0, s);
     return launch<float, double, float, true, true>(L, T, M, U, L, (const float*)Y, M, (float*)Ty, ld, S, 1, nullptr, 0, s);
@@ -344,7 +372,12 @@ int launch_project_stream(int dtype, const void* Y, size_t T, size_t M, size_t L
 
 // Yhat[t][m] = sum_l Tyhat[l][t] * sqrt(S_l) * U[m][l]:  i = t, j = m, k = l;  A = Tyhat (i-contiguous, lda = ld);  B = U (k-contiguous, ldb = L)
 int launch_unproject_stream(int dtype, const void* Tyhat, size_t T, size_t ld, size_t M, size_t L, const double* U, const float* U32,
-                            const double* S /* sqrtS */, void* Yhat, hipStream_t s) {
+                            const double* S /* sqrtS */, void* Yhat, hipStream_t s, bool tiled) {
+    if (tiled) {      // Tyhat segment-major (ld unused): the same three kernels with the tiled A operand
+        if (dtype == 0) return launch<double, double, double, true, true, false, SEGM_A>(T, M, L, (const double*)Tyhat, 0, U, L, (double*)Yhat, M, nullptr, 0, S, 1, s);
+        if (U32) return launch<float, float, float, true, true, false, SEGM_A>(T, M, L, (const float*)Tyhat, 0, U32, L, (float*)Yhat, M, nullptr, 0, S, 1, s);
+        return launch<float, float, double, true, true, false, SEGM_A>(T, M, L, (const float*)Tyhat, 0, U, L, (float*)Yhat, M, nullptr, 0, S, 1, s);
+    }
     if (dtype == 0) return launch<double, double, double, true, true>(T, M, L, (const double*)Tyhat, ld, U, L, (double*)Yhat, M, nullptr, 0, S, 1, s);
     if (U32) return launch<float, float, float, true, true>(T, M, L, (const float*)Tyhat, ld, U32, L, (float*)Yhat, M, nullptr, 0, S, 1, s);
     return launch<float, float, double, true, true>(T, M, L, (const float*)Tyhat, ld, U, L, (float*)Yhat, M, nullptr, 0, S, 1, s);

@@ -1402,7 +1402,8 @@ void filter_split_plan(int dtype, size_t T, size_t L, int* nsplit, size_t* Tslic
     *nsplit = (int)want; *Tslice = per * seg; *nbig = (int)big;
 }
 
-// series-major <-> segment-major copies (callers that hold one layout and want the other; the projection GEMM writes either directly)
+// series-major <-> segment-major copies, for callers that hold one layout and want the other.  A pipeline from observations needs neither
+// pass: moihgp_project_stream_tiled writes the segment-major layout and moihgp_unproject_stream_tiled reads it (gemm_mfma.hip SEGM_C / SEGM_A).
 template <typename T>
 __global__ void __launch_bounds__(256) retile_kernel(const T* __restrict__ src, T* __restrict__ dst, size_t L, size_t Tlen, size_t ld, int to_tiled) {
     constexpr size_t SEGT = 4096 / sizeof(T);

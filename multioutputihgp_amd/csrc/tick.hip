@@ -341,8 +341,10 @@ __global__ void ugrad_kernel(size_t M, size_t L, const double* __restrict__ S, c
 // One workgroup per tick; a tick without NaN costs one pass over its M observations and leaves at once.  fp64 inside whatever the
 // stream type.  k > kLsMaxMissing or fewer observed outputs than latents: the column stays NaN (the recursion then treats the tick as
 // missing; the reference would factor a singular matrix there).
+// TILED: Ty is segment-major [ceil(Tn / SEG)][L][SEG] (include/moihgp.h), where tick t of latent l sits at s SEG (L - 1) + l SEG + t with
+// s = t / SEG: the tick's column is a base and the stride SEG, worked out once (the address function of gemm_mfma.hip's tiled C store).
 
-template <typename T>
+template <typename T, bool TILED = false>
 __global__ void __launch_bounds__(256) ls_project_kernel(const T* __restrict__ Y, size_t Tn, size_t M, size_t L, const double* __restrict__ U,
                                                          const double* __restrict__ invsqrtS, T* __restrict__ Ty, size_t ld) {
     extern __shared__ double lsm[];
@@ -404,10 +406,13 @@ __global__ void __launch_bounds__(256) ls_project_kernel(const T* __restrict__ Y
     }
     __syncthreads();
     // a = r + U_miss^T c;  Ty[l][t] = S_l^-1/2 a_l  (moihgp.h:177)
+    constexpr size_t SEG = 4096 / sizeof(T);
+    T* col = TILED ? Ty + (t / SEG) * SEG * (L - 1) + t : Ty + t;
+    const size_t step = TILED ? SEG : ld;
     for (size_t l = tid; l < L; l += 256) {
         double a = r[l];
         for (int i = 0; i < k; i++) a = fma(U[(size_t)miss[i] * L + l], G[i * kk + k], a);
-        Ty[l * ld + t] = (T)(invsqrtS[l] * a);
+        col[l * step] = (T)(invsqrtS[l] * a);
     }
 }
 
@@ -550,16 +555,20 @@ void launch_ortho_defect(const double* G, size_t L, double* out, hipStream_t s) 
 }
 
 int launch_project_stream_missing(int dtype, const void* Y, size_t T, size_t M, size_t L, const double* U, const double* invsqrtS, void* Ty, size_t ld,
-                                   hipStream_t s) {
+                                   hipStream_t s, bool tiled) {
     if (T == 0 || L == 0) return 0;
     if (!ls_project_fits(L)) return 0;                 // (the NaN columns stand: include/moihgp.h)
     const size_t smem = ls_project_lds_bytes(L);
+    auto go = [&](auto kernel, auto* y, auto* ty) {
+        if (smem > 48 * 1024) MOIHGP_HIP_FATAL(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+        hipLaunchKernelGGL(kernel, dim3((unsigned)T), dim3(256), smem, s, y, T, M, L, U, invsqrtS, ty, ld);
+    };
     if (dtype == 0) {
-        if (smem > 48 * 1024) MOIHGP_HIP_FATAL(hipFuncSetAttribute(reinterpret_cast<const void*>(ls_project_kernel<double>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        hipLaunchKernelGGL(ls_project_kernel<double>, dim3((unsigned)T), dim3(256), smem, s, (const double*)Y, T, M, L, U, invsqrtS, (double*)Ty, ld);
+        if (tiled) go(ls_project_kernel<double, true>, (const double*)Y, (double*)Ty);
+        else go(ls_project_kernel<double, false>, (const double*)Y, (double*)Ty);
     } else {
-        if (smem > 48 * 1024) MOIHGP_HIP_FATAL(hipFuncSetAttribute(reinterpret_cast<const void*>(ls_project_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        hipLaunchKernelGGL(ls_project_kernel<float>, dim3((unsigned)T), dim3(256), smem, s, (const float*)Y, T, M, L, U, invsqrtS, (float*)Ty, ld);
+        if (tiled) go(ls_project_kernel<float, true>, (const float*)Y, (float*)Ty);
+        else go(ls_project_kernel<float, false>, (const float*)Y, (float*)Ty);
     }
     MOIHGP_HIP_FATAL(hipGetLastError());
     return 0;

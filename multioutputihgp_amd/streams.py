@@ -6,7 +6,10 @@ Stream layout: SERIES-MAJOR `[L, ld]` (one contiguous row per latent), fp32 or f
 the reference callers (`for y in data: gp.step(x, y)`, example.py:40-42; moihgp_online.h:61-70;
 moihgp_regression.h:42-50) becomes ONE call over T ticks.
 
-Ordering (include/moihgp.h "ordering contract"): `filter`, `grad`, `project_stream`, `unproject_stream` are asynchronous on
+Segment-major streams `[ceil(T / SEG), L, SEG]` (`alloc_stream_tiled`): `project_stream_tiled` -> `LatentBank.filter_tiled` ->
+`unproject_stream_tiled` is the same pipeline without a copy between layouts; `filter_outputs` picks one of the two.
+
+Ordering (include/moihgp.h "ordering contract"): `filter`, `grad`, `project_stream`, `unproject_stream` (and the tiled forms) are asynchronous on
 the torch stream they are given and read the handle's tables; `LatentBank.update`, `MOIHGP.update` and `set_mixing` first wait
 (on the device) for all such work already enqueued through the handle, then rewrite the tables and return when they are
 complete -- an update issued behind pipelined sweeps neither overtakes them nor needs a host synchronisation from the caller.
@@ -430,6 +433,84 @@ def unproject_stream(gp, Tyhat: torch.Tensor, T: int, stream=None) -> torch.Tens
     _check(lib.moihgp_unproject_stream(gp.handle, _DT[Tyhat.dtype], C.c_void_p(Tyhat.data_ptr()), T, Tyhat.stride(0),
                                        C.c_void_p(Yhat.data_ptr()), _stream_ptr(stream)), lib)
     return Yhat
+
+
+def _check_observations(gp, Y: torch.Tensor):
+    if not isinstance(Y, torch.Tensor) or not Y.is_cuda or Y.dtype not in _DT or Y.dim() != 2 or not Y.is_contiguous() or Y.shape[1] != gp.num_output:
+        raise ValueError("Y must be a contiguous CUDA tensor [T, M] (float32/float64)")
+
+
+def _check_tiled(name: str, Tt: torch.Tensor, L: int, T: int, dtype, device):
+    """ValueError unless Tt is a contiguous, 16-byte aligned tensor [ceil(T / SEG), L, SEG] of `dtype` on `device`."""
+    seg = seg_ticks(dtype)
+    nseg = (T + seg - 1) // seg
+    if (not isinstance(Tt, torch.Tensor) or Tt.device != device or Tt.dtype != dtype or not Tt.is_contiguous() or tuple(Tt.shape) != (nseg, L, seg)
+            or Tt.data_ptr() % 16 != 0):
+        raise ValueError(f"{name} must be a contiguous, 16-byte aligned {dtype} tensor [ceil(T / {seg}) = {nseg}, L = {L}, {seg}] on {device}")
+
+
+def project_stream_tiled(gp, Y: torch.Tensor, out: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
+    """`project_stream` with the result in the SEGMENT-MAJOR layout [ceil(T / SEG), L, SEG] that `LatentBank.filter_tiled` sweeps
+    (moihgp_project_stream_tiled): the same arithmetic and the same values bit for bit, missing outputs included, without a `tile_stream` pass.
+    `out` (optional) must be exactly that shape, contiguous, of Y's dtype and device.  Ticks past T in the last tile are not written: they keep
+    whatever the buffer held (the sweep ignores them)."""
+    lib = load_library()
+    _check_observations(gp, Y)
+    T, L = Y.shape[0], gp.num_latent
+    if out is None:
+        out = alloc_stream_tiled(L, T, Y.dtype, Y.device)
+    _check_tiled("out", out, L, T, Y.dtype, Y.device)
+    _check(lib.moihgp_project_stream_tiled(gp.handle, _DT[Y.dtype], C.c_void_p(Y.data_ptr()), T, C.c_void_p(out.data_ptr()), _stream_ptr(stream)), lib)
+    return out
+
+
+def unproject_stream_tiled(gp, Tt: torch.Tensor, T: int, stream=None) -> torch.Tensor:
+    """`unproject_stream` from a SEGMENT-MAJOR stream [ceil(T / SEG), L, SEG], e.g. the yhat of `LatentBank.filter_tiled`
+    (moihgp_unproject_stream_tiled): Yhat [T, M], the same values bit for bit, without an `untile_stream` pass.  Ticks past T in the last tile
+    are never read (they may hold anything, NaN included)."""
+    lib = load_library()
+    if isinstance(T, bool) or not isinstance(T, (int, np.integer)) or T < 0:
+        raise ValueError("T must be a non-negative integer")
+    T = int(T)
+    if not isinstance(Tt, torch.Tensor) or not Tt.is_cuda or Tt.dtype not in _DT:
+        raise ValueError("Tt must be a CUDA tensor (float32/float64)")
+    _check_tiled("Tt", Tt, gp.num_latent, T, Tt.dtype, Tt.device)
+    Yhat = torch.empty((T, gp.num_output), dtype=Tt.dtype, device=Tt.device)
+    _check(lib.moihgp_unproject_stream_tiled(gp.handle, _DT[Tt.dtype], C.c_void_p(Tt.data_ptr()), T, C.c_void_p(Yhat.data_ptr()), _stream_ptr(stream)), lib)
+    return Yhat
+
+
+AUTO_TILED_ABOVE = 1024     # filter_outputs(layout="auto"): above this many latents both layouts run the same one-wavefront-per-latent sweep kernel
+
+
+def filter_outputs(gp, Y: torch.Tensor, layout: str = "auto", want_nll: bool = True, stream=None):
+    """Filtered outputs of a tick-major observation stream Y [T, M] (NaN = missing output) with the parameters of `gp` (a pywrapper.MOIHGP), from a
+    zero state: project -> LatentBank.filter / filter_tiled -> un-project, asynchronous on the torch stream.
+
+    Returns (Yhat [T, M] in Y's dtype, x [L, d] end state, nll [L] fp64 or None).  Yhat[t] is what `gp.step` returns at tick t of the loop
+    `for y in Y: x, yhat = gp.step(x, y)`.  Ticks with missing outputs are projected as project_stream does it: a tick with more than 64 missing
+    outputs or fewer than L observed ones is treated as missing as a whole.
+
+    layout: "series" -- series-major streams throughout; "tiled" -- segment-major streams throughout (project_stream_tiled -> filter_tiled ->
+    unproject_stream_tiled, no retile pass; stacked models raise MoihgpError with rc 3); "auto" -- tiled exactly when the model is not stacked
+    and has more than 1024 latents, where both layouts run the same sweep kernel (bit-equal results) and the tiled one moves a cold stream
+    faster; at fewer latents the series-major entry has time-split and team kernels the tiled one lacks, so "auto" stays series-major."""
+    if layout not in ("auto", "series", "tiled"):
+        raise ValueError('layout must be "auto", "series" or "tiled"')
+    _check_observations(gp, Y)
+    T = Y.shape[0]
+    bank = LatentBank.from_handle(gp)
+    if layout == "auto":
+        layout = "tiled" if (not bank.stacked and bank.L > AUTO_TILED_ABOVE) else "series"
+    # (the intermediate buffers and the zero start state belong to the stream the kernels run on)
+    with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
+        if layout == "tiled":
+            Tt = project_stream_tiled(gp, Y, stream=stream)
+            yhat, x, nll = bank.filter_tiled(Tt, T, want_nll=want_nll, stream=stream)
+            return unproject_stream_tiled(gp, yhat, T, stream=stream), x, nll
+        Ty = project_stream(gp, Y, stream=stream)
+        yhat, x, nll = bank.filter(Ty, T=T, want_nll=want_nll, stream=stream)
+        return unproject_stream(gp, yhat, T, stream=stream), x, nll
 
 
 def smooth_outputs(gp, Y: torch.Tensor, stream=None):
