@@ -307,6 +307,51 @@ int moihgp_forecast_stream(moihgp_gp* gp, int dtype, const void* Ty, size_t T, s
 int moihgp_forecast_tail(moihgp_gp* gp, int dtype, const void* x, size_t n, void* tail, size_t ld_out, void* stream);
 int moihgp_forecast_variances(moihgp_gp* gp, const int* horizons, size_t K, double* var);
 
+/* ---- seeded steady-state posterior samples of whole streams (not in the reference) -----------------------------------------------------------
+ * Joint draws over time of every latent given ALL the ticks of the stream: the smoother's mean plus a stationary deviation process with the
+ * steady-state posterior's covariance across time.  The textbook backward sampler (x~[t] = xf[t] + G (x~[t+1] - A xf[t]) + w, w ~ N(0, PF - G P G^T))
+ * does not exist for these models: the reference's Matern-5/2 (lam = sqrt(3)/l, matern52ss.h:42) makes Q and PF - G P G^T indefinite.  The SCALAR
+ * output process is valid all the same: with the smoother's G and Ps, r[k] = H G^k Ps H^T is the posterior covariance between interior ticks k apart,
+ * and the sampler draws from its innovations realization, one scalar normal per tick.  Per latent, with h = e0, N = Ps h, r0 = Ps_00:
+ *     Sigma  solves   sigma^2 = r0 - Sigma_00,   B = G (N - Sigma h) / sigma^2,   Sigma = G Sigma G^T + sigma^2 B B^T
+ * (the limit of the iteration from Sigma = 0; 64 such steps, then up to 8 Newton steps dSigma - Ac dSigma Ac^T = F(Sigma), Ac = G - B h^T).  It is
+ * accepted by what it reproduces: with r^[0] = Sigma_00 + sigma^2, r^[k] = (G^{k-1} (G Sigma h + sigma^2 B))_0,
+ *     acov_err = max_{k < 64} |r^[k] - r[k]| / r0 <= 1e-9,  sigma^2 > 0 and everything finite, or that latent gets status 2.
+ * Lc is the lower Cholesky factor of sym(Sigma) (a pivot <= 0 gives a zero column).
+ * Noise: Philox4x32-10 (Random123's constants), key = (seed low word, seed high word), counter = (q, latent0 + l, sample0 + s, tag):
+ *     tag 0, q = t / 4: the four words give the normals n[4q] .. n[4q+3];  tag 1, q = 0: the start normals g_0 .. g_3.
+ * A pair of words (a, b) -- words (0, 1) and words (2, 3) -- gives two normals, in fp32 whatever the stream's type (an fp32 and an fp64 stream see
+ * the same noise), with the accurate library functions:
+ *     u1 = ((a >> 8) + 0.5) 2^-24,  u2 = ((b >> 8) + 0.5) 2^-24,  rho = sqrtf(-2 logf(u1)),  normals  rho cosf(2 pi u2),  rho sinf(2 pi u2).
+ * Per sample s and latent l, backward in time (fp64 arithmetic for both stream types):
+ *     u[T-1] = Lc g;    for t = T-1 .. 0:   e = sigma n[t];   o[t] = u[t]_0 + e;   u[t-1] = G u[t] + B e
+ *     samples[s][l][t] = ysmooth[l][t] + o[t]
+ * with ysmooth exactly what moihgp_smooth_stream writes for the same arguments: missing ticks and the start state act through the mean only.
+ * The deviation process is stationary and independent of the data: it is the exact posterior covariance in the interior of a long gap-free stream;
+ * within a few correlation lengths of the two ends and of missing ticks it is under-dispersed (at the last tick the exact variance is var_filtered,
+ * not var_smoothed).  This is the same steady-state approximation the smoother's var_smoothed already makes.  Latents are independent a posteriori
+ * under the OILMM, so un-projecting plane s (moihgp_unproject_stream) gives a joint sample of all outputs (of the function f; no observation noise).
+ * moihgp_sample_stream: Ty, x_in, x, ld_in as moihgp_smooth_stream.  ysmooth [L][ld_out] is required and is written by the smoothing the call runs;
+ *   samples [S][L][ld_out], plane s starting s * plane_stride elements after samples; strides and alignment as moihgp_forecast_stream.  ysmooth and
+ *   samples must not overlap Ty or each other.  seed: 64 bits; sample0, latent0: offsets of this call's samples and latents in the counter, so that
+ *   calls for ranges of samples, or banks that hold ranges of latents, reproduce the rows of one large call bit for bit.  status: DEVICE int [L] or
+ *   NULL: 0 ok; 1 Kalman DARE not converged (as the smoother: ysmooth row, end state and sample rows NaN); 2 realization not accepted (sample rows
+ *   NaN; ysmooth row and end state the smoother's).  Returns 1 (and launches nothing) for nsamples outside 1 .. 65535, bad strides or alignment, an
+ *   overlap; 3 for stacked models.  Asynchronous on `stream`, with the handle's stream bookkeeping as for a smooth; the realization's tables are
+ *   built behind the smoother's, on the first call that needs them after a table rewrite.
+ *   Option "sample_path" (moihgp_set_option): -1 automatic (the time-parallel scan kernel; a serial fp64 walk for latents whose G fails the
+ *   smoother's growth bound), 0 scan for every latent, 1 serial fp64 walk for every latent.
+ * moihgp_sample_noise: the normals above without a handle -- noise [S][L][ld] (DEVICE float, n[t] of latent latent0 + l and sample sample0 + s at
+ *   [s][l][t], t < T <= ld) and start [S][L][4] (DEVICE float or NULL: g_0 .. g_3).  Asynchronous on `stream`.  The way to audit a draw.
+ * moihgp_get_sampler: latent l's B [d], sigma^2, Sigma [d*d], Lc [d*d] (row-major), acov_err and status, to HOST buffers (any may be NULL).
+ *   Synchronises. */
+int moihgp_sample_stream(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x,
+                         size_t nsamples, unsigned long long seed, unsigned sample0, unsigned latent0,
+                         void* ysmooth, size_t ld_out, void* samples, size_t plane_stride, int* status, void* stream);
+int moihgp_sample_noise(unsigned long long seed, unsigned latent0, size_t L, unsigned sample0, size_t S, size_t T,
+                        float* noise, size_t ld, float* start, void* stream);
+int moihgp_get_sampler(moihgp_gp* gp, size_t l, double* B, double* sigma2, double* Sigma, double* Lc, double* acov_err, int* status);
+
 /* As above plus the hyper-parameter sensitivities (ihgp.h:54) and the per-latent NLL gradient
  * (ihgp.h:216-220), summed over ticks:
  *   dx   [L][P][d] in/out (dtype);  grad [L][P] doubles out. */

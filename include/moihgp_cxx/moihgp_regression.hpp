@@ -149,6 +149,49 @@ public:
         for (size_t t = 0; t < T; t++) for (size_t m = 0; m < M; m++) Ys[t][m] = flat[t * M + m];
         return Ys;
     }
+    // (not in the reference) Seeded joint posterior samples of the whole series with the current parameters (include/moihgp.h
+    // moihgp_sample_stream): element [s][t] is sample s of every output at tick t given ALL of Y -- the smoothed mean of predictSmoothed() plus a
+    // draw of the steady-state deviation process (exact covariance in the interior of a long gap-free series, under-dispersed near its ends and
+    // missing ticks), from a zero start state.  The same seed gives the same samples.  fp64 on the device: project_stream -> sample_stream ->
+    // unproject_stream per sample.  Throws std::invalid_argument for nsamples outside 1 .. 65535 and std::runtime_error on a non-zero status
+    // (1 Kalman DARE not converged, 2 sampling realization not accepted).  Missing outputs (NaN) are projected as in predictSmoothed().
+    std::vector<std::vector<Vector>> sampleSmoothed(const std::vector<Vector>& Y, size_t nsamples, unsigned long long seed = 0) {
+        if (nsamples < 1 || nsamples > 65535) throw std::invalid_argument("sampleSmoothed: nsamples must be 1 .. 65535");
+        const size_t T = Y.size(), M = _num_output, L = _num_latent, ld = (T + 1) / 2 * 2, S = nsamples;
+        std::vector<std::vector<Vector>> Ys(S, std::vector<Vector>(T, Vector(M, 0.0)));
+        if (T == 0) return Ys;
+        Vector flat(T * M), zeros(L * _dim, 0.0);
+        for (size_t t = 0; t < T; t++) for (size_t m = 0; m < M; m++) flat[t * M + m] = Y[t][m];
+        moihgp_dvec_ctx* ctx = moihgp_dvec_ctx_new();
+        const size_t nst = (L + 1) / 2;                             // status words: L ints in doubles' storage
+        double *dY = moihgp_dvec_alloc(T * M), *dTy = moihgp_dvec_alloc(L * ld), *dys = moihgp_dvec_alloc(L * ld), *dsm = moihgp_dvec_alloc(S * L * ld),
+               *dx = moihgp_dvec_alloc(L * _dim), *dst = moihgp_dvec_alloc(nst);
+        int rc = (ctx && dY && dTy && dys && dsm && dx && dst) ? 0 : 4;
+        Vector st(nst, 0.0);
+        void* s = ctx ? moihgp_dvec_ctx_stream(ctx) : nullptr;
+        moihgp_gp* h = _moihgp->handle();
+        if (!rc) rc = moihgp_dvec_upload(ctx, dY, flat.data(), T * M);
+        if (!rc) rc = moihgp_dvec_upload(ctx, dx, zeros.data(), L * _dim);
+        if (!rc) rc = moihgp_project_stream(h, MOIHGP_F64, dY, T, dTy, ld, s);
+        if (!rc) rc = moihgp_sample_stream(h, MOIHGP_F64, dTy, T, ld, dx, dx, S, seed, 0, 0, dys, ld, dsm, L * ld, reinterpret_cast<int*>(dst), s);
+        if (!rc) rc = moihgp_dvec_download(ctx, st.data(), dst, nst);
+        for (size_t k = 0; k < S && !rc; k++) {
+            rc = moihgp_unproject_stream(h, MOIHGP_F64, dsm + k * L * ld, T, ld, dY, s);
+            if (!rc) rc = moihgp_dvec_download(ctx, flat.data(), dY, T * M);
+            if (!rc) rc = moihgp_dvec_sync(ctx);
+            if (!rc) for (size_t t = 0; t < T; t++) for (size_t m = 0; m < M; m++) Ys[k][t][m] = flat[t * M + m];
+        }
+        if (ctx) { moihgp_dvec_sync(ctx); moihgp_release_stream(h, s); }
+        for (double* p : {dY, dTy, dys, dsm, dx, dst}) if (p) moihgp_dvec_free(p);
+        if (ctx) moihgp_dvec_ctx_del(ctx);
+        if (rc) throw std::runtime_error(std::string("sampleSmoothed: ") + moihgp_last_error());
+        std::vector<int> status(2 * nst, 0);
+        std::memcpy(status.data(), st.data(), sizeof(double) * nst);
+        for (size_t l = 0; l < L; l++)
+            if (status[l] != 0) throw std::runtime_error("sampleSmoothed: latent " + std::to_string(l) + " has status " + std::to_string(status[l]) +
+                                                         (status[l] == 1 ? " (the Kalman DARE did not converge)" : " (the sampling realization was not accepted)"));
+        return Ys;
+    }
     // (not in the reference) Forecasts `horizon` ticks ahead at every tick of the series with the current parameters (include/moihgp.h
     // moihgp_forecast_stream, Kalman-form gains): element t is the mean of every output at tick t + horizon given Y[0..t], from a zero start
     // state, where the reference would call step(x, y) and then `horizon` prediction-only steps per tick.  fp64 on the device:

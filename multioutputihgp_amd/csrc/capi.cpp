@@ -138,13 +138,20 @@ struct moihgp_gp {
     hipEvent_t fc_ev = nullptr;
     bool fc_ev_set = false;
     int opt_forecast_path = -1;          // option "forecast_path": -1 automatic, 0 scan kernel, 1 serial fp64
+    // posterior sampling (moihgp_sample_stream): the realization's per-latent tables, built lazily behind the smoother's (ensure_sampler) for the
+    // constant blocks of version sp_version
+    double* dsp = nullptr;
+    unsigned long long sp_version = 0;
+    hipStream_t sp_built_on = nullptr;
+    hipEvent_t sp_ev = nullptr;
+    int opt_sample_path = -1;            // option "sample_path": -1 automatic, 0 scan kernel, 1 serial fp64
 
     TickArgs tick() const { return TickArgs{d, M, L, cb64, dU, dS, dsqrtS, dinvsqrtS, dsigma, (threading || lik1_full) ? 1 : 0, P, cbd64}; }
 };
 
 static void gp_free(moihgp_gp* g) {
     if (!g) return;
-    void* ptrs[] = {g->dU, g->dS, g->dsqrtS, g->dinvsqrtS, g->dsigma, g->dparams, g->cb64, g->cb32, g->dx, g->dpart, g->dTy, g->dUty, g->dTyhat, g->dloss, g->dgrad, g->dscratch, g->dwork, g->dpolar, g->dfallback, g->dwin, g->dunstable, g->dxscratch, g->cbd64, g->dU32, g->dhp, g->dlink, g->dwinmiss, g->dtp64, g->dtp32, g->dxc64, g->dxc32, g->dlinkflags, g->dgap, g->drescue_idx, g->drescue, g->drescue_const, g->dsm, g->dfc64, g->dfc32};
+    void* ptrs[] = {g->dU, g->dS, g->dsqrtS, g->dinvsqrtS, g->dsigma, g->dparams, g->cb64, g->cb32, g->dx, g->dpart, g->dTy, g->dUty, g->dTyhat, g->dloss, g->dgrad, g->dscratch, g->dwork, g->dpolar, g->dfallback, g->dwin, g->dunstable, g->dxscratch, g->cbd64, g->dU32, g->dhp, g->dlink, g->dwinmiss, g->dtp64, g->dtp32, g->dxc64, g->dxc32, g->dlinkflags, g->dgap, g->drescue_idx, g->drescue, g->drescue_const, g->dsm, g->dfc64, g->dfc32, g->dsp};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (void* p : g->pinned) (void)hipHostUnregister(p);
@@ -156,6 +163,7 @@ static void gp_free(moihgp_gp* g) {
     if (g->order_ev) (void)hipEventDestroy(g->order_ev);
     if (g->sm_ev) (void)hipEventDestroy(g->sm_ev);
     if (g->fc_ev) (void)hipEventDestroy(g->fc_ev);
+    if (g->sp_ev) (void)hipEventDestroy(g->sp_ev);
     if (g->stream) (void)hipStreamDestroy(g->stream);
     delete g;
 }
@@ -1133,6 +1141,91 @@ int moihgp_forecast_variances(moihgp_gp* gp, const int* horizons, size_t K, doub
     return guard_rc([&] { return forecast_variances_impl(gp, horizons, K, var); });
 }
 
+// ---- seeded steady-state posterior sampling (sampler.hip) ---------------------------------------------------------------------------------------
+// The realization's tables follow the smoother's: built on the first call that needs them after a table rewrite (which bumps cb_version), on that
+// call's stream, with sp_ev as sm_ev above.  The rewrites themselves do nothing for them.
+static int ensure_sampler(moihgp_gp* g, hipStream_t s) {
+    if (int rc = ensure_smoother(g, s)) return rc;
+    if (!g->dsp) g->dsp = dev_alloc<double>(g->L * (size_t)sp_size(g->d));
+    if (!g->sp_ev) MOIHGP_HIP_FATAL(hipEventCreateWithFlags(&g->sp_ev, hipEventDisableTiming));
+    if (g->sp_version != g->cb_version) {
+        launch_sampler_tables(g->d, g->dsm, g->L, g->dsp, s);
+        MOIHGP_HIP_FATAL(hipEventRecord(g->sp_ev, s));
+        g->sp_built_on = s;
+        g->sp_version = g->cb_version;
+    } else if (s != g->sp_built_on) {
+        MOIHGP_HIP_FATAL(hipStreamWaitEvent(s, g->sp_ev, 0));
+    }
+    return 0;
+}
+
+static int sample_stream_impl(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x, size_t nsamples,
+                              unsigned long long seed, unsigned sample0, unsigned latent0, void* ys, size_t ld_out, void* samples, size_t plane_stride,
+                              int* status, void* stream) {
+    if (int rc = check_stream_args(gp, dtype, Ty, T, ld_in, x)) return rc;
+    if (!x_in) { set_last_error("null start state"); return 1; }
+    if (nsamples < 1 || nsamples > 65535) { set_last_error("sample: nsamples (%zu) must be 1 .. 65535", nsamples); return 1; }
+    const size_t es = dtype == MOIHGP_F64 ? 8 : 4, epv = 16 / es;
+    if (int rc = check_out_rows(ys, "ysmooth", T, 'T', ld_out, es)) return rc;
+    if (int rc = check_out_rows(samples, "sample buffer", T, 'T', ld_out, es)) return rc;
+    if (samples && (plane_stride % epv != 0 || plane_stride < gp->L * ld_out)) {
+        set_last_error("plane_stride (%zu) must be a multiple of %zu and >= L * ld_out (%zu)", plane_stride, epv, gp->L * ld_out);
+        return 1;
+    }
+    const size_t sample_elems = (nsamples - 1) * plane_stride + gp->L * ld_out;
+    if (int rc = check_no_overlap(Ty, gp->L * ld_in, ys, gp->L * ld_out, T, es, "ysmooth must not overlap the input stream")) return rc;
+    if (int rc = check_no_overlap(Ty, gp->L * ld_in, samples, sample_elems, T, es, "the sample buffer must not overlap the input stream")) return rc;
+    if (int rc = check_no_overlap(ys, gp->L * ld_out, samples, sample_elems, T, es, "the sample buffer must not overlap ysmooth")) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = ensure_sampler(gp, s)) return rc;
+    note_user_stream(gp, s);
+    launch_smooth_stream(gp->d, dtype, Ty, T, ld_in, gp->L, gp->dsm, x_in, x, ys, ld_out, nullptr, gp->opt_smoother_path, s);
+    launch_sample_stream(gp->d, dtype, T, gp->L, gp->dsm, gp->dsp, ys, ld_out, samples, plane_stride, (int)nsamples, seed, sample0, latent0, status,
+                         gp->opt_sample_path, s);
+    return 0;
+}
+
+static int sample_noise_impl(unsigned long long seed, unsigned latent0, size_t L, unsigned sample0, size_t S, size_t T, float* noise, size_t ld, float* start,
+                             void* stream) {
+    if (T > 0 && L > 0 && S > 0 && !noise) { set_last_error("sample_noise: null noise buffer"); return 1; }
+    if (ld < T) { set_last_error("sample_noise: ld (%zu) must be >= T", ld); return 1; }
+    launch_sample_noise(seed, latent0, L, sample0, S, T, noise, ld, start, (hipStream_t)stream);
+    return 0;
+}
+
+static int get_sampler_impl(moihgp_gp* gp, size_t l, double* B, double* sigma2, double* Sigma, double* Lc, double* acov_err, int* status) {
+    if (!gp || l >= gp->L) { set_last_error("get_sampler: bad latent index"); return 1; }
+    if (int rc = ensure_sampler(gp, gp->stream)) return rc;
+    MOIHGP_HIP_FATAL(hipEventSynchronize(gp->sp_ev));
+    const size_t bs = (size_t)sp_size(gp->d);
+    std::vector<double> b(bs);
+    MOIHGP_HIP_FATAL(hipMemcpyAsync(b.data(), gp->dsp + l * bs, sizeof(double) * bs, hipMemcpyDeviceToHost, gp->stream));
+    MOIHGP_HIP_FATAL(hipStreamSynchronize(gp->stream));
+    auto cp = [&](double* dst, int o, int n) { if (dst) std::memcpy(dst, b.data() + o, sizeof(double) * n); };
+    dispatch_dim(gp->d, [&](auto dim) {
+        constexpr int D = decltype(dim)::value;
+        using P = SP<D>;
+        cp(B, P::B, D); cp(sigma2, P::SIGMA2, 1); cp(Sigma, P::SG, P::NN); cp(Lc, P::LC, P::NN); cp(acov_err, P::ERR, 1);
+        if (status) *status = (int)b[P::STATUS];
+    });
+    return 0;
+}
+
+int moihgp_sample_stream(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x, size_t nsamples,
+                         unsigned long long seed, unsigned sample0, unsigned latent0, void* ysmooth, size_t ld_out, void* samples, size_t plane_stride,
+                         int* status, void* stream) {
+    return guard_rc([&] {
+        return sample_stream_impl(gp, dtype, Ty, T, ld_in, x_in, x, nsamples, seed, sample0, latent0, ysmooth, ld_out, samples, plane_stride, status, stream);
+    });
+}
+int moihgp_sample_noise(unsigned long long seed, unsigned latent0, size_t L, unsigned sample0, size_t S, size_t T, float* noise, size_t ld, float* start,
+                        void* stream) {
+    return guard_rc([&] { return sample_noise_impl(seed, latent0, L, sample0, S, T, noise, ld, start, stream); });
+}
+int moihgp_get_sampler(moihgp_gp* gp, size_t l, double* B, double* sigma2, double* Sigma, double* Lc, double* acov_err, int* status) {
+    return guard_rc([&] { return get_sampler_impl(gp, l, B, sigma2, Sigma, Lc, acov_err, status); });
+}
+
 int moihgp_stream_retile(int dtype, const void* src, void* dst, size_t L, size_t T, size_t ld, int to_tiled, void* stream) {
     return guard_rc([&] {
         if (dtype != MOIHGP_F64 && dtype != MOIHGP_F32) { set_last_error("dtype must be MOIHGP_F64 or MOIHGP_F32"); return 1; }
@@ -1475,6 +1568,7 @@ int moihgp_set_option(moihgp_gp* gp, const char* name, long value) {
     if (n == "filter_plain_x") { if (value < -1 || value > 1) { set_last_error("filter_plain_x: -1 (automatic), 0 (never), 1 (always: the stacked filter's kernels for Matern-3/2 and -5/2)"); return 1; } gp->opt_filter_plain_x = (int)value; return 0; }
     if (n == "filter_team") { if (value < -1 || value > 2) { set_last_error("filter_team: -1 (automatic), 0 (never), 1 (whenever the stream fits), 2 (the 32-tick-chunk form only)"); return 1; } gp->opt_filter_team = (int)value; return 0; }
     if (n == "filter_maxlinks") { if (value < -1 || value > 64) { set_last_error("filter_maxlinks: -1 (automatic) .. 64"); return 1; } gp->opt_filter_maxlinks = (int)value; return 0; }
+    if (n == "sample_path") { if (value < -1 || value > 1) { set_last_error("sample_path: -1 (automatic), 0 (scan kernel), 1 (serial fp64)"); return 1; } gp->opt_sample_path = (int)value; return 0; }
     if (n == "smoother_path") { if (value < -1 || value > 1) { set_last_error("smoother_path: -1 (automatic), 0 (scan kernels), 1 (serial fp64)"); return 1; } gp->opt_smoother_path = (int)value; return 0; }
     if (n == "forecast_path") { if (value < -1 || value > 1) { set_last_error("forecast_path: -1 (automatic), 0 (scan kernel), 1 (serial fp64)"); return 1; } gp->opt_forecast_path = (int)value; return 0; }
     if (n == "filter_variant") {

@@ -209,6 +209,15 @@ void launch_forecast_tables(int kernel, int d, const double* cb64, const double*
 void launch_forecast_stream(int d, int dtype, const void* Ty, size_t T, size_t ld_in, size_t L, const double* t64, const float* t32, const void* x_in,
                             void* x, void* fc, size_t ld_out, size_t plane_stride, int K, int* status, int path, hipStream_t stream);
 void launch_forecast_tail(int d, int dtype, const double* cb64, size_t L, const void* x, size_t n, void* tail, size_t ld_out, hipStream_t stream);
+// sampler.hip: seeded steady-state posterior samples (include/moihgp.h moihgp_sample_stream).  Per-latent fp64 block SP<D> of sp_size(d) doubles
+// (stream_tables.h) from the smoother's blocks sm; ysm: the smoothed means [L][ld_out] the deviations are added to; samples [S][L][ld_out], planes
+// plane_stride apart.  path as launch_smooth_stream's.  status: 0 ok, 1 Kalman DARE failed, 2 realization failed (sample rows NaN).
+void launch_sampler_tables(int d, const double* sm, size_t L, double* sp, hipStream_t stream);
+void launch_sample_stream(int d, int dtype, size_t T, size_t L, const double* sm, const double* sp, const void* ysm, size_t ld_out, void* samples,
+                          size_t plane_stride, int nsamples, unsigned long long seed, unsigned sample0, unsigned latent0, int* status, int path,
+                          hipStream_t stream);
+void launch_sample_noise(unsigned long long seed, unsigned latent0, size_t L, unsigned sample0, size_t S, size_t T, float* noise, size_t ld, float* start,
+                         hipStream_t stream);
 // series-major [L][ld] <-> segment-major [ceil(T / SEG)][L][SEG] (to_tiled != 0: src is series-major; ticks past T are written as zeros)
 int launch_stream_retile(int dtype, const void* src, void* dst, size_t L, size_t T, size_t ld, int to_tiled, hipStream_t stream);
 // recursion.hip: batched sweeps over series-major streams.

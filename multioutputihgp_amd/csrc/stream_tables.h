@@ -1,5 +1,5 @@
-// stream_tables.h -- the per-latent table blocks of the whole-stream smoother (smoother.hip) and forecasts (forecast.hip), the chunk geometry
-// their chunk powers are built for, and the (d, dtype) dispatch of their launchers.  Read by both files and by capi.cpp.
+// stream_tables.h -- the per-latent table blocks of the whole-stream smoother (smoother.hip), forecasts (forecast.hip) and sampler (sampler.hip), the
+// chunk geometry their chunk powers are built for, and the (d, dtype) dispatch of their launchers.  Read by those files and by capi.cpp.
 #pragma once
 #include "common.h"
 #include <type_traits>
@@ -35,8 +35,22 @@ struct FT {
     static constexpr int SIZE = (STATUS + 1 + 3) / 4 * 4;
 };
 
+// per-latent sampler block (fp64), offsets in doubles: the innovations realization of the smoother's steady-state autocovariance (sampler.hip),
+// next to the latent's SM<D> block (which holds G, G^kScanChunk and Ps)
+template <int D>
+struct SP {
+    static constexpr int NN = D * D;
+    static constexpr int B = 0, LC = B + D, SG = LC + NN;       // B, Lc = chol(Sigma), Sigma
+    static constexpr int SIGMA = SG + NN, SIGMA2 = SIGMA + 1;
+    static constexpr int ERR = SIGMA2 + 1;                      // max_{k < 64} |r^[k] - r[k]| / r0, the acceptance figure
+    static constexpr int GROWTH = ERR + 1;                      // max inf-norm of G^k, k <= 2 kScanChunk, and of G^kScanSeg
+    static constexpr int STATUS = GROWTH + 1;                   // 0 ok, 1 the Kalman DARE failed, 2 the realization failed
+    static constexpr int SIZE = (STATUS + 1 + 1) / 2 * 2;
+};
+
 constexpr int sm_size(int d) { return d == 2 ? SM<2>::SIZE : SM<3>::SIZE; }
 constexpr int fc_size(int d) { return d == 2 ? FT<2>::SIZE : FT<3>::SIZE; }
+constexpr int sp_size(int d) { return d == 2 ? SP<2>::SIZE : SP<3>::SIZE; }
 
 // f(std::integral_constant<int, D>) for the state dimension d (2 or 3); f(Tv(), std::integral_constant<int, D>) for the stream's scalar too
 template <typename F>

@@ -176,7 +176,7 @@ class LatentBank:
 
     def set_option(self, name: str, value: int):
         """Per-handle tuning / test hooks (include/moihgp.h moihgp_set_option): "filter_split" (0 automatic, 1 off, n slices),
-        "filter_maxlinks", "filter_variant" (tuning builds only), "smoother_path", "forecast_path" (-1 automatic, 0 scan kernels, 1 serial fp64)."""
+        "filter_maxlinks", "filter_variant" (tuning builds only), "smoother_path", "forecast_path", "sample_path" (-1 automatic, 0 scan kernels, 1 serial fp64)."""
         _check(self._lib.moihgp_set_option(self._h, name.encode(), int(value)), self._lib)
 
     def update(self, params_LP):
@@ -320,6 +320,17 @@ class LatentBank:
                 raise ValueError(f"{name} must be a contiguous [L, d] tensor of the stream dtype")
         return x, (x if x_start is None else x_start)
 
+    def _ysmooth_buffer(self, Ty: torch.Tensor, T: int, ysmooth: Optional[torch.Tensor]):
+        """(ysmooth, ld_out) of smooth / sample: the caller's buffer, checked, or a fresh one."""
+        if ysmooth is None:
+            ysmooth = alloc_stream(self.L, max(T, 1), Ty.dtype, Ty.device)[:, :T]
+        elif (not ysmooth.is_cuda or ysmooth.dtype != Ty.dtype or ysmooth.dim() != 2 or ysmooth.stride(1) != 1 or ysmooth.shape[0] != self.L
+              or ysmooth.shape[1] < T or (self.L > 1 and ysmooth.stride(0) < padded_len(T, Ty.dtype))
+              or ysmooth.stride(0) % (2 if Ty.dtype == torch.float64 else 4) != 0):
+            raise ValueError("ysmooth must be a CUDA tensor [L, >=T] of the stream's dtype, unit stride along time, row stride a multiple of "
+                             "16 bytes and >= T rounded up to it")
+        return ysmooth, (ysmooth.stride(0) if self.L > 1 else padded_len(max(T, 1), Ty.dtype))
+
     def smooth(self, Ty: torch.Tensor, T: Optional[int] = None, x: Optional[torch.Tensor] = None, x_start: Optional[torch.Tensor] = None,
                ysmooth: Optional[torch.Tensor] = None, stream=None):
         """Steady-state RTS smoothing of T ticks for every latent (include/moihgp.h moihgp_smooth_stream): the posterior mean at every tick
@@ -332,14 +343,7 @@ class LatentBank:
         if self.stacked:
             raise MoihgpError("smooth: stacked models are not supported (Matern-3/2 and -5/2 only)", 3)
         x, start = self._start_state(Ty, x, x_start)
-        if ysmooth is None:
-            ysmooth = alloc_stream(self.L, max(T, 1), Ty.dtype, Ty.device)[:, :T]
-        elif (not ysmooth.is_cuda or ysmooth.dtype != Ty.dtype or ysmooth.dim() != 2 or ysmooth.stride(1) != 1 or ysmooth.shape[0] != self.L
-              or ysmooth.shape[1] < T or (self.L > 1 and ysmooth.stride(0) < padded_len(T, Ty.dtype))
-              or ysmooth.stride(0) % (2 if Ty.dtype == torch.float64 else 4) != 0):
-            raise ValueError("ysmooth must be a CUDA tensor [L, >=T] of the stream's dtype, unit stride along time, row stride a multiple of "
-                             "16 bytes and >= T rounded up to it")
-        ld_out = ysmooth.stride(0) if self.L > 1 else padded_len(max(T, 1), Ty.dtype)
+        ysmooth, ld_out = self._ysmooth_buffer(Ty, T, ysmooth)
         status = torch.empty((self.L,), dtype=torch.int32, device=Ty.device)
         rc = self._lib.moihgp_smooth_stream(self._h, _DT[Ty.dtype], C.c_void_p(Ty.data_ptr()), T, ld,
                                             C.c_void_p(start.data_ptr()), C.c_void_p(x.data_ptr()),
@@ -363,6 +367,61 @@ class LatentBank:
         _check(self._lib.moihgp_latent_variances(self._h, vf.ctypes.data_as(c_double_p), vs.ctypes.data_as(c_double_p)), self._lib)
         return vf, vs
 
+    def sample(self, Ty: torch.Tensor, nsamples: int, seed: int = 0, sample0: int = 0, latent0: int = 0, T: Optional[int] = None,
+               x: Optional[torch.Tensor] = None, x_start: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+               ysmooth: Optional[torch.Tensor] = None, stream=None):
+        """Seeded steady-state posterior samples of T ticks for every latent (include/moihgp.h moihgp_sample_stream): samples[s, l] is the smoothed
+        mean of latent l plus a draw of the stationary deviation process with the steady-state posterior's covariance across time (exact in the
+        interior of a long gap-free stream, under-dispersed near the ends and missing ticks, as var_smoothed).  The noise is Philox4x32-10 keyed by
+        `seed` (64 bits) and counted by (tick, latent0 + l, sample0 + s): calls for ranges of samples or latents reproduce one large call bit for bit.
+
+        Returns (samples [S, L, >=T], ysmooth [L, >=T], x [L, d] end state, status [L] int32: 0 ok, 1 Kalman DARE not converged (all NaN),
+        2 realization not accepted (sample rows NaN, ysmooth as smooth())).  Asynchronous on the current torch stream.  `x`, `x_start`, `ysmooth` as
+        smooth(); `out` (optional) [S, L, >=T] as forecast()'s; `out` and `ysmooth` must not overlap Ty or each other."""
+        T, ld = self._check_stream(Ty, T)
+        S = int(nsamples)
+        if not 1 <= S <= 65535:
+            raise ValueError("nsamples must be 1 .. 65535")
+        seed, sample0, latent0 = int(seed), int(sample0), int(latent0)
+        if not (0 <= seed < 1 << 64 and 0 <= sample0 < 1 << 32 and 0 <= latent0 < 1 << 32):
+            raise ValueError("seed must be in 0 .. 2^64 - 1, sample0 and latent0 in 0 .. 2^32 - 1")
+        if self.stacked:
+            raise MoihgpError("sample: stacked models are not supported (Matern-3/2 and -5/2 only)", 3)
+        x, start = self._start_state(Ty, x, x_start)
+        if out is None:
+            ysmooth, ld_out = self._ysmooth_buffer(Ty, T, ysmooth)
+            out = torch.empty((S, self.L, ld_out), dtype=Ty.dtype, device=Ty.device)[:, :, :T]
+        ld_out, plane = _forecast_out_strides(out, S, self.L, T, Ty)
+        # one row stride serves both buffers in the C entry: means without a buffer of their own take the sample planes' stride, and a caller's
+        # `ysmooth` of another stride receives a copy
+        ys_user = None
+        if ysmooth is None:
+            ysmooth = torch.empty((self.L, ld_out), dtype=Ty.dtype, device=Ty.device)[:, :T]
+        elif self._ysmooth_buffer(Ty, T, ysmooth)[1] != ld_out and self.L > 1:
+            ys_user, ysmooth = ysmooth, torch.empty((self.L, ld_out), dtype=Ty.dtype, device=Ty.device)[:, :T]
+        status = torch.empty((self.L,), dtype=torch.int32, device=Ty.device)
+        rc = self._lib.moihgp_sample_stream(self._h, _DT[Ty.dtype], C.c_void_p(Ty.data_ptr()), T, ld,
+                                            C.c_void_p(start.data_ptr()), C.c_void_p(x.data_ptr()), S, seed, sample0, latent0,
+                                            C.c_void_p(ysmooth.data_ptr()), ld_out, C.c_void_p(out.data_ptr()), plane,
+                                            C.c_void_p(status.data_ptr()), _stream_ptr(stream))
+        _check(rc, self._lib)
+        if ys_user is not None:
+            with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
+                ys_user[:, :T].copy_(ysmooth)
+            ysmooth = ys_user
+        return out, ysmooth, x, status
+
+    def sampler(self, l: int) -> dict:
+        """The sampler's realization of latent l (moihgp_get_sampler): B, sigma2, Sigma, Lc, acov_err, status."""
+        d = self.d
+        out = dict(B=np.zeros(d), sigma2=np.zeros(1), Sigma=np.zeros((d, d)), Lc=np.zeros((d, d)), acov_err=np.zeros(1))
+        st = C.c_int(0)
+        ptrs = [out[k].ctypes.data_as(c_double_p) for k in ("B", "sigma2", "Sigma", "Lc", "acov_err")]
+        _check(self._lib.moihgp_get_sampler(self._h, int(l), *ptrs, C.byref(st)), self._lib)
+        out["sigma2"] = float(out["sigma2"][0])
+        out["acov_err"] = float(out["acov_err"][0])
+        out["status"] = int(st.value)
+        return out
 
     def forecast(self, Ty: torch.Tensor, horizons, T: Optional[int] = None, x: Optional[torch.Tensor] = None, x_start: Optional[torch.Tensor] = None,
                  out: Optional[torch.Tensor] = None, gains: str = "kalman", stream=None):
@@ -535,6 +594,42 @@ def smooth_outputs(gp, Y: torch.Tensor, stream=None):
     U, S = prm[:M * L].reshape(M, L), prm[M * L:M * L + L]
     _, vs = bank.latent_variances()
     return Ys, (U ** 2) @ (S * vs)
+
+
+def sample_noise(seed: int, L: int, S: int, T: int, latent0: int = 0, sample0: int = 0, want_start: bool = True, device="cuda", stream=None):
+    """The sampler's normals without a handle (moihgp_sample_noise): (noise [S, L, T] float32, start [S, L, 4] float32 or None) with noise[s, l, t]
+    the normal of tick t, latent latent0 + l, sample sample0 + s, and start the four start normals.  The way to audit a draw."""
+    lib = load_library()
+    ld = padded_len(max(T, 1), torch.float32)
+    noise = torch.empty((S, L, ld), dtype=torch.float32, device=device)      # (empty: nothing of torch's runs on a stream of its own here)
+    start = torch.empty((S, L, 4), dtype=torch.float32, device=device) if want_start else None
+    _check(lib.moihgp_sample_noise(int(seed), int(latent0), L, int(sample0), S, T, C.c_void_p(noise.data_ptr()), ld,
+                                   C.c_void_p(start.data_ptr()) if want_start else None, _stream_ptr(stream)), lib)
+    return noise[:, :, :T], start
+
+
+def sample_outputs(gp, Y: torch.Tensor, nsamples: int, seed: int = 0, stream=None):
+    """Joint posterior samples of the outputs for a tick-major observation stream Y [T, M] (NaN = missing output) with the parameters of `gp` (a
+    pywrapper.MOIHGP), from a zero state: project_stream -> LatentBank.sample -> unproject_stream per plane (the latents are independent a
+    posteriori, so un-projecting a plane of latent samples gives a joint sample of all outputs; of the function, without observation noise).
+
+    Returns (Ys [S, T, M] in Y's dtype, Ymean [T, M] the smoothed outputs, var_Y [M] fp64 numpy as smooth_outputs).  Raises MoihgpError on any
+    non-zero status (Kalman DARE not converged, or the sampler's realization not accepted).  Missing outputs as smooth_outputs."""
+    T = Y.shape[0]
+    bank = LatentBank.from_handle(gp)
+    Ty = project_stream(gp, Y, stream=stream)
+    smp, ys, _, status = bank.sample(Ty, nsamples, seed=seed, T=T, stream=stream)
+    Ys = torch.stack([unproject_stream(gp, smp[s], T, stream=stream) for s in range(smp.shape[0])])
+    Ymean = unproject_stream(gp, ys, T, stream=stream)
+    st = status.cpu().numpy()           # (synchronises)
+    if st.any():
+        raise MoihgpError(f"sample_outputs: {int((st == 1).sum())} latent(s) whose Kalman DARE did not converge, {int((st == 2).sum())} whose "
+                          "sampling realization was not accepted; their rows are NaN and so is every output that mixes them", 1)
+    M, L = gp.num_output, gp.num_latent
+    prm = gp.params
+    U, S = prm[:M * L].reshape(M, L), prm[M * L:M * L + L]
+    _, vs = bank.latent_variances()
+    return Ys, Ymean, (U ** 2) @ (S * vs)
 
 
 def forecast_outputs(gp, Y: torch.Tensor, horizons, tail: int = 0, gains: str = "kalman", stream=None):
