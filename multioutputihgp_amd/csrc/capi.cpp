@@ -46,6 +46,14 @@ static T* dev_alloc(size_t n) {
 
 using namespace moihgp;
 
+// Per-latent device tables derived from the constant blocks, built lazily (ensure_tables)
+struct LazyTables {
+    double* d = nullptr;
+    unsigned long long version = 0;   // cb_version they were built for (0: never)
+    hipStream_t built_on = nullptr;   // stream that carried the last build; ev marks its end for the other streams / host reads
+    hipEvent_t ev = nullptr;
+};
+
 struct moihgp_gp {
     int kernel = 0;
     double dt = 0;
@@ -125,10 +133,7 @@ struct moihgp_gp {
     std::vector<hipEvent_t> prof_ev;
     int prof_n = 0;
     // steady-state RTS smoother (moihgp_smooth_stream): its per-latent tables, built lazily on the first smooth after a table rewrite
-    double* dsm = nullptr;
-    bool sm_stale = true;
-    hipStream_t sm_built_on = nullptr;   // stream that carried the last build; sm_ev marks its end for the other streams / host reads
-    hipEvent_t sm_ev = nullptr;
+    LazyTables sm;
     int opt_smoother_path = -1;          // option "smoother_path": -1 automatic, 0 scan kernels, 1 serial fp64
     // multi-horizon forecasts (moihgp_forecast_stream): the per-call tables (fp64 and fp32 copy), rebuilt by every call for its horizons on its
     // stream; fc_ev marks the end of the last call that used them, and a call on another stream waits for it before it rewrites them
@@ -138,12 +143,8 @@ struct moihgp_gp {
     hipEvent_t fc_ev = nullptr;
     bool fc_ev_set = false;
     int opt_forecast_path = -1;          // option "forecast_path": -1 automatic, 0 scan kernel, 1 serial fp64
-    // posterior sampling (moihgp_sample_stream): the realization's per-latent tables, built lazily behind the smoother's (ensure_sampler) for the
-    // constant blocks of version sp_version
-    double* dsp = nullptr;
-    unsigned long long sp_version = 0;
-    hipStream_t sp_built_on = nullptr;
-    hipEvent_t sp_ev = nullptr;
+    // posterior sampling (moihgp_sample_stream): the realization's per-latent tables, built lazily behind the smoother's (ensure_sampler)
+    LazyTables sp;
     int opt_sample_path = -1;            // option "sample_path": -1 automatic, 0 scan kernel, 1 serial fp64
 
     TickArgs tick() const { return TickArgs{d, M, L, cb64, dU, dS, dsqrtS, dinvsqrtS, dsigma, (threading || lik1_full) ? 1 : 0, P, cbd64}; }
@@ -151,7 +152,7 @@ struct moihgp_gp {
 
 static void gp_free(moihgp_gp* g) {
     if (!g) return;
-    void* ptrs[] = {g->dU, g->dS, g->dsqrtS, g->dinvsqrtS, g->dsigma, g->dparams, g->cb64, g->cb32, g->dx, g->dpart, g->dTy, g->dUty, g->dTyhat, g->dloss, g->dgrad, g->dscratch, g->dwork, g->dpolar, g->dfallback, g->dwin, g->dunstable, g->dxscratch, g->cbd64, g->dU32, g->dhp, g->dlink, g->dwinmiss, g->dtp64, g->dtp32, g->dxc64, g->dxc32, g->dlinkflags, g->dgap, g->drescue_idx, g->drescue, g->drescue_const, g->dsm, g->dfc64, g->dfc32, g->dsp};
+    void* ptrs[] = {g->dU, g->dS, g->dsqrtS, g->dinvsqrtS, g->dsigma, g->dparams, g->cb64, g->cb32, g->dx, g->dpart, g->dTy, g->dUty, g->dTyhat, g->dloss, g->dgrad, g->dscratch, g->dwork, g->dpolar, g->dfallback, g->dwin, g->dunstable, g->dxscratch, g->cbd64, g->dU32, g->dhp, g->dlink, g->dwinmiss, g->dtp64, g->dtp32, g->dxc64, g->dxc32, g->dlinkflags, g->dgap, g->drescue_idx, g->drescue, g->drescue_const, g->sm.d, g->dfc64, g->dfc32, g->sp.d};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (void* p : g->pinned) (void)hipHostUnregister(p);
@@ -161,9 +162,9 @@ static void gp_free(moihgp_gp* g) {
     if (g->hflag) (void)hipHostFree(g->hflag);
     for (hipEvent_t e : g->prof_ev) (void)hipEventDestroy(e);
     if (g->order_ev) (void)hipEventDestroy(g->order_ev);
-    if (g->sm_ev) (void)hipEventDestroy(g->sm_ev);
+    if (g->sm.ev) (void)hipEventDestroy(g->sm.ev);
     if (g->fc_ev) (void)hipEventDestroy(g->fc_ev);
-    if (g->sp_ev) (void)hipEventDestroy(g->sp_ev);
+    if (g->sp.ev) (void)hipEventDestroy(g->sp.ev);
     if (g->stream) (void)hipStreamDestroy(g->stream);
     delete g;
 }
@@ -204,6 +205,30 @@ static void caller_waits(moihgp_gp* g, hipStream_t s) {
     MOIHGP_HIP_FATAL(hipStreamWaitEvent(s, g->order_ev, 0));
 }
 
+// LazyTables are built by the first call that needs them after a table rewrite (which bumps cb_version), on that call's stream s: build() launches
+// into t.d (block doubles per latent), ev marks the end of the build, and a call on another stream (or a host read) waits for it.  A rewrite waits
+// for every stream that carried batched work and synchronises, so no sweep still reads the old tables when the next build overwrites them.
+template <typename Build>
+static void ensure_tables(moihgp_gp* g, LazyTables& t, size_t block, hipStream_t s, Build&& build) {
+    if (!t.d) t.d = dev_alloc<double>(g->L * block);
+    if (!t.ev) MOIHGP_HIP_FATAL(hipEventCreateWithFlags(&t.ev, hipEventDisableTiming));
+    if (t.version != g->cb_version) {
+        build();
+        MOIHGP_HIP_FATAL(hipEventRecord(t.ev, s));
+        t.built_on = s; t.version = g->cb_version;
+    } else if (s != t.built_on) {
+        MOIHGP_HIP_FATAL(hipStreamWaitEvent(s, t.ev, 0));
+    }
+}
+// host copy of the blocks of latents [l0, l0 + n) of tables that ensure_tables has just seen to (through the handle's stream)
+static std::vector<double> read_tables(moihgp_gp* g, const LazyTables& t, size_t block, size_t l0, size_t n) {
+    MOIHGP_HIP_FATAL(hipEventSynchronize(t.ev));
+    std::vector<double> out(n * block);
+    MOIHGP_HIP_FATAL(hipMemcpyAsync(out.data(), t.d + l0 * block, sizeof(double) * n * block, hipMemcpyDeviceToHost, g->stream));
+    MOIHGP_HIP_FATAL(hipStreamSynchronize(g->stream));
+    return out;
+}
+
 static void upload_mixing(moihgp_gp* g) {
     if (g->latents_only) return;
     order_after_sweeps(g);
@@ -221,8 +246,7 @@ static void upload_mixing(moihgp_gp* g) {
 static void run_ihgp_update(moihgp_gp* g) {
     order_after_sweeps(g);
     g->hp_valid = false;
-    g->sm_stale = true;                 // the smoother's tables follow on the next smooth (nothing is computed for them here)
-    g->cb_version++;
+    g->cb_version++;                    // the smoother's and the sampler's tables follow on their next use (nothing is computed for them here)
     MOIHGP_HIP_FATAL(hipMemcpyAsync(g->dparams, g->igp.data(), sizeof(double) * g->L * g->P, hipMemcpyHostToDevice, g->stream));
     if (kernel_stack(g->kernel)) {
         // the sensitivities cost nine more 100-iteration Lyapunov solves per latent at d = 12: only for handles that use them
@@ -751,6 +775,13 @@ static int check_stream_args(moihgp_gp* gp, int dtype, const void* Ty, size_t T,
     return 0;
 }
 
+// ... of the whole-stream smoother, forecasts and sampler, which also take the state before tick 0
+static int check_sweep_call(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld, const void* x_in, const void* x) {
+    if (int rc = check_stream_args(gp, dtype, Ty, T, ld, x)) return rc;
+    if (!x_in) { set_last_error("null start state"); return 1; }
+    return 0;
+}
+
 int moihgp_filter_stream(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld, void* x, void* yhat, double* nll, void* stream) {
     return moihgp_filter_stream_io(gp, dtype, Ty, T, ld, x, x, yhat, nll, nullptr, stream);
 }
@@ -945,21 +976,10 @@ int moihgp_filter_stream_tiled(moihgp_gp* gp, int dtype, const void* Ty, size_t 
 }
 
 // ---- steady-state RTS smoother (smoother.hip) ----------------------------------------------------------------------------------------------
-// Its tables are built on the first smooth after a table rewrite, on that call's stream; sm_ev marks the end of the build, and a smooth on
-// another stream (or a host read) waits for it.  A rewrite (run_ihgp_update) waits for every stream that carried batched work and
-// synchronises, so no smooth still reads the old tables when the next build overwrites them.
+// Its tables are built on the first smooth after a table rewrite, on that call's stream (ensure_tables).
 static int ensure_smoother(moihgp_gp* g, hipStream_t s) {
     if (kernel_stack(g->kernel)) { set_last_error("smoother: stacked models are not supported (Matern-3/2 and -5/2 only)"); return 3; }
-    if (!g->dsm) g->dsm = dev_alloc<double>(g->L * (size_t)sm_size(g->d));
-    if (!g->sm_ev) MOIHGP_HIP_FATAL(hipEventCreateWithFlags(&g->sm_ev, hipEventDisableTiming));
-    if (g->sm_stale) {
-        launch_smoother_tables(kernel_base(g->kernel), g->d, g->cb64, g->L, g->dsm, s);
-        MOIHGP_HIP_FATAL(hipEventRecord(g->sm_ev, s));
-        g->sm_built_on = s;
-        g->sm_stale = false;
-    } else if (s != g->sm_built_on) {
-        MOIHGP_HIP_FATAL(hipStreamWaitEvent(s, g->sm_ev, 0));
-    }
+    ensure_tables(g, g->sm, (size_t)sm_size(g->d), s, [&] { launch_smoother_tables(kernel_base(g->kernel), g->d, g->cb64, g->L, g->sm.d, s); });
     return 0;
 }
 
@@ -976,7 +996,14 @@ static int check_out_rows(const void* out, const char* name, size_t n, char n_na
     }
     return 0;
 }
-// ... which may not overlap the input stream (in_elems, out_elems scalars of es bytes; nothing to check without output or ticks)
+// ... whose planes of L rows lie plane_stride scalars apart: a multiple of the 16-byte vector that holds a whole plane
+static int check_planes(const void* out, size_t plane_stride, size_t L, size_t ld_out, size_t es) {
+    const size_t epv = 16 / es;
+    if (!out || (plane_stride % epv == 0 && plane_stride >= L * ld_out)) return 0;
+    set_last_error("plane_stride (%zu) must be a multiple of %zu and >= L * ld_out (%zu)", plane_stride, epv, L * ld_out);
+    return 1;
+}
+// ... and which may not overlap the input stream (in_elems, out_elems scalars of es bytes; nothing to check without output or ticks)
 static int check_no_overlap(const void* in, size_t in_elems, const void* out, size_t out_elems, size_t T, size_t es, const char* msg) {
     const uintptr_t a0 = (uintptr_t)in, a1 = a0 + in_elems * es, b0 = (uintptr_t)out, b1 = b0 + out_elems * es;
     if (out && T > 0 && a0 < b1 && b0 < a1) { set_last_error("%s", msg); return 1; }
@@ -985,8 +1012,7 @@ static int check_no_overlap(const void* in, size_t in_elems, const void* out, si
 
 static int smooth_stream_impl(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x, void* ys, size_t ld_out,
                               int* status, void* stream) {
-    if (int rc = check_stream_args(gp, dtype, Ty, T, ld_in, x)) return rc;
-    if (!x_in) { set_last_error("null start state"); return 1; }
+    if (int rc = check_sweep_call(gp, dtype, Ty, T, ld_in, x_in, x)) return rc;
     const size_t es = dtype == MOIHGP_F64 ? 8 : 4;
     if (int rc = check_out_rows(ys, "ysmooth", T, 'T', ld_out, es)) return rc;
     // the backward sweep reads y after the forward one wrote the predicted means: the two may not overlap
@@ -994,18 +1020,14 @@ static int smooth_stream_impl(moihgp_gp* gp, int dtype, const void* Ty, size_t T
     hipStream_t s = (hipStream_t)stream;
     if (int rc = ensure_smoother(gp, s)) return rc;
     note_user_stream(gp, s);
-    launch_smooth_stream(gp->d, dtype, Ty, T, ld_in, gp->L, gp->dsm, x_in, x, ys, ld_out, status, gp->opt_smoother_path, s);
+    launch_smooth_stream(gp->d, dtype, Ty, T, ld_in, gp->L, gp->sm.d, x_in, x, ys, ld_out, status, gp->opt_smoother_path, s);
     return 0;
 }
 
 // host copy of the smoother blocks of latents [l0, l0 + n), built first if stale (on the handle's stream)
 static int read_smoother(moihgp_gp* gp, size_t l0, size_t n, std::vector<double>& out) {
     if (int rc = ensure_smoother(gp, gp->stream)) return rc;
-    MOIHGP_HIP_FATAL(hipEventSynchronize(gp->sm_ev));
-    const size_t bs = (size_t)sm_size(gp->d);
-    out.resize(n * bs);
-    MOIHGP_HIP_FATAL(hipMemcpyAsync(out.data(), gp->dsm + l0 * bs, sizeof(double) * n * bs, hipMemcpyDeviceToHost, gp->stream));
-    MOIHGP_HIP_FATAL(hipStreamSynchronize(gp->stream));
+    out = read_tables(gp, gp->sm, (size_t)sm_size(gp->d), l0, n);
     return 0;
 }
 
@@ -1073,17 +1095,13 @@ static int check_horizons(const int* horizons, size_t K, FcHorizons& hz) {
 
 static int forecast_stream_impl(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x, const int* horizons, size_t K,
                                 void* fc, size_t ld_out, size_t plane_stride, int gains, int* status, void* stream) {
-    if (int rc = check_stream_args(gp, dtype, Ty, T, ld_in, x)) return rc;
-    if (!x_in) { set_last_error("null start state"); return 1; }
+    if (int rc = check_sweep_call(gp, dtype, Ty, T, ld_in, x_in, x)) return rc;
     FcHorizons hz;
     if (int rc = check_horizons(horizons, K, hz)) return rc;
     if (gains != MOIHGP_GAINS_KALMAN && gains != MOIHGP_GAINS_HANDLE) { set_last_error("forecast: gains must be MOIHGP_GAINS_KALMAN (0) or MOIHGP_GAINS_HANDLE (1)"); return 1; }
-    const size_t es = dtype == MOIHGP_F64 ? 8 : 4, epv = 16 / es;
+    const size_t es = dtype == MOIHGP_F64 ? 8 : 4;
     if (int rc = check_out_rows(fc, "forecast buffer", T, 'T', ld_out, es)) return rc;
-    if (fc && (plane_stride % epv != 0 || plane_stride < gp->L * ld_out)) {
-        set_last_error("plane_stride (%zu) must be a multiple of %zu and >= L * ld_out (%zu)", plane_stride, epv, gp->L * ld_out);
-        return 1;
-    }
+    if (int rc = check_planes(fc, plane_stride, gp->L, ld_out, es)) return rc;
     // a segment of y is read after earlier segments' planes were written: the two may not overlap
     if (int rc = check_no_overlap(Ty, gp->L * ld_in, fc, (K - 1) * plane_stride + gp->L * ld_out, T, es, "the forecast buffer must not overlap the input stream")) return rc;
     if (kernel_stack(gp->kernel)) { set_last_error("forecast: stacked models are not supported (Matern-3/2 and -5/2 only)"); return 3; }
@@ -1092,7 +1110,7 @@ static int forecast_stream_impl(moihgp_gp* gp, int dtype, const void* Ty, size_t
         if (int rc = ensure_smoother(gp, s)) return rc;
     note_user_stream(gp, s);
     forecast_begin(gp, s);
-    launch_forecast_tables(kernel_base(gp->kernel), gp->d, gp->cb64, gp->dsm, gp->L, hz, (int)K, gains, gp->dfc64, gp->dfc32, s);
+    launch_forecast_tables(kernel_base(gp->kernel), gp->d, gp->cb64, gp->sm.d, gp->L, hz, (int)K, gains, gp->dfc64, gp->dfc32, s);
     launch_forecast_stream(gp->d, dtype, Ty, T, ld_in, gp->L, gp->dfc64, gp->dfc32, x_in, x, fc, ld_out, plane_stride, (int)K, status,
                            gp->opt_forecast_path, s);
     forecast_end(gp, s);
@@ -1119,7 +1137,7 @@ static int forecast_variances_impl(moihgp_gp* gp, const int* horizons, size_t K,
     if (int rc = ensure_smoother(gp, gp->stream)) return rc;
     if (!var) return 0;
     forecast_begin(gp, gp->stream);
-    launch_forecast_tables(kernel_base(gp->kernel), gp->d, gp->cb64, gp->dsm, gp->L, hz, (int)K, MOIHGP_GAINS_KALMAN, gp->dfc64, gp->dfc32, gp->stream);
+    launch_forecast_tables(kernel_base(gp->kernel), gp->d, gp->cb64, gp->sm.d, gp->L, hz, (int)K, MOIHGP_GAINS_KALMAN, gp->dfc64, gp->dfc32, gp->stream);
     const size_t bs = (size_t)fc_size(gp->d), vo = (size_t)(gp->d == 2 ? FT<2>::VAR : FT<3>::VAR);
     std::vector<double> b(gp->L * bs);
     MOIHGP_HIP_FATAL(hipMemcpyAsync(b.data(), gp->dfc64, sizeof(double) * b.size(), hipMemcpyDeviceToHost, gp->stream));
@@ -1142,36 +1160,22 @@ int moihgp_forecast_variances(moihgp_gp* gp, const int* horizons, size_t K, doub
 }
 
 // ---- seeded steady-state posterior sampling (sampler.hip) ---------------------------------------------------------------------------------------
-// The realization's tables follow the smoother's: built on the first call that needs them after a table rewrite (which bumps cb_version), on that
-// call's stream, with sp_ev as sm_ev above.  The rewrites themselves do nothing for them.
+// The realization's tables follow the smoother's, by the same protocol (ensure_tables).  The rewrites themselves do nothing for them.
 static int ensure_sampler(moihgp_gp* g, hipStream_t s) {
     if (int rc = ensure_smoother(g, s)) return rc;
-    if (!g->dsp) g->dsp = dev_alloc<double>(g->L * (size_t)sp_size(g->d));
-    if (!g->sp_ev) MOIHGP_HIP_FATAL(hipEventCreateWithFlags(&g->sp_ev, hipEventDisableTiming));
-    if (g->sp_version != g->cb_version) {
-        launch_sampler_tables(g->d, g->dsm, g->L, g->dsp, s);
-        MOIHGP_HIP_FATAL(hipEventRecord(g->sp_ev, s));
-        g->sp_built_on = s;
-        g->sp_version = g->cb_version;
-    } else if (s != g->sp_built_on) {
-        MOIHGP_HIP_FATAL(hipStreamWaitEvent(s, g->sp_ev, 0));
-    }
+    ensure_tables(g, g->sp, (size_t)sp_size(g->d), s, [&] { launch_sampler_tables(g->d, g->sm.d, g->L, g->sp.d, s); });
     return 0;
 }
 
 static int sample_stream_impl(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x, size_t nsamples,
                               unsigned long long seed, unsigned sample0, unsigned latent0, void* ys, size_t ld_out, void* samples, size_t plane_stride,
                               int* status, void* stream) {
-    if (int rc = check_stream_args(gp, dtype, Ty, T, ld_in, x)) return rc;
-    if (!x_in) { set_last_error("null start state"); return 1; }
+    if (int rc = check_sweep_call(gp, dtype, Ty, T, ld_in, x_in, x)) return rc;
     if (nsamples < 1 || nsamples > 65535) { set_last_error("sample: nsamples (%zu) must be 1 .. 65535", nsamples); return 1; }
-    const size_t es = dtype == MOIHGP_F64 ? 8 : 4, epv = 16 / es;
+    const size_t es = dtype == MOIHGP_F64 ? 8 : 4;
     if (int rc = check_out_rows(ys, "ysmooth", T, 'T', ld_out, es)) return rc;
     if (int rc = check_out_rows(samples, "sample buffer", T, 'T', ld_out, es)) return rc;
-    if (samples && (plane_stride % epv != 0 || plane_stride < gp->L * ld_out)) {
-        set_last_error("plane_stride (%zu) must be a multiple of %zu and >= L * ld_out (%zu)", plane_stride, epv, gp->L * ld_out);
-        return 1;
-    }
+    if (int rc = check_planes(samples, plane_stride, gp->L, ld_out, es)) return rc;
     const size_t sample_elems = (nsamples - 1) * plane_stride + gp->L * ld_out;
     if (int rc = check_no_overlap(Ty, gp->L * ld_in, ys, gp->L * ld_out, T, es, "ysmooth must not overlap the input stream")) return rc;
     if (int rc = check_no_overlap(Ty, gp->L * ld_in, samples, sample_elems, T, es, "the sample buffer must not overlap the input stream")) return rc;
@@ -1179,8 +1183,8 @@ static int sample_stream_impl(moihgp_gp* gp, int dtype, const void* Ty, size_t T
     hipStream_t s = (hipStream_t)stream;
     if (int rc = ensure_sampler(gp, s)) return rc;
     note_user_stream(gp, s);
-    launch_smooth_stream(gp->d, dtype, Ty, T, ld_in, gp->L, gp->dsm, x_in, x, ys, ld_out, nullptr, gp->opt_smoother_path, s);
-    launch_sample_stream(gp->d, dtype, T, gp->L, gp->dsm, gp->dsp, ys, ld_out, samples, plane_stride, (int)nsamples, seed, sample0, latent0, status,
+    launch_smooth_stream(gp->d, dtype, Ty, T, ld_in, gp->L, gp->sm.d, x_in, x, ys, ld_out, nullptr, gp->opt_smoother_path, s);
+    launch_sample_stream(gp->d, dtype, T, gp->L, gp->sm.d, gp->sp.d, ys, ld_out, samples, plane_stride, (int)nsamples, seed, sample0, latent0, status,
                          gp->opt_sample_path, s);
     return 0;
 }
@@ -1196,11 +1200,7 @@ static int sample_noise_impl(unsigned long long seed, unsigned latent0, size_t L
 static int get_sampler_impl(moihgp_gp* gp, size_t l, double* B, double* sigma2, double* Sigma, double* Lc, double* acov_err, int* status) {
     if (!gp || l >= gp->L) { set_last_error("get_sampler: bad latent index"); return 1; }
     if (int rc = ensure_sampler(gp, gp->stream)) return rc;
-    MOIHGP_HIP_FATAL(hipEventSynchronize(gp->sp_ev));
-    const size_t bs = (size_t)sp_size(gp->d);
-    std::vector<double> b(bs);
-    MOIHGP_HIP_FATAL(hipMemcpyAsync(b.data(), gp->dsp + l * bs, sizeof(double) * bs, hipMemcpyDeviceToHost, gp->stream));
-    MOIHGP_HIP_FATAL(hipStreamSynchronize(gp->stream));
+    const std::vector<double> b = read_tables(gp, gp->sp, (size_t)sp_size(gp->d), l, 1);
     auto cp = [&](double* dst, int o, int n) { if (dst) std::memcpy(dst, b.data() + o, sizeof(double) * n); };
     dispatch_dim(gp->d, [&](auto dim) {
         constexpr int D = decltype(dim)::value;

@@ -17,9 +17,9 @@
 //   forecast_serial_kernel   one lane per latent, fp64, tick by tick: latents whose M fails the growth bound (rho(AKHA) > 1 occurs with the
 //                            handle's gains), option "forecast_path" = 1, and every status word.
 //   forecast_tail_kernel     tail[l][j] = H A^(j+1) x_l, fp64: each lane powers A to its first index and then strides by A^64.
-// The chunk-scan machinery of the sweep is scan_sweep.h (shared with smoother.hip), the block layout FT<D> stream_tables.h.  The growth figure
-// is the largest inf-norm of the powers of M up to 2 kScanChunk and of M^kScanSeg (the smoother's figure also covers its G, which no forecast
-// uses: it is not consulted), held against scan_growth_bound<Ta>().
+// The chunk-scan machinery of the sweep is scan_sweep.h (shared with smoother.hip and sampler.hip), the block layout FT<D> stream_tables.h.  The
+// growth figure is the largest inf-norm of the powers of M up to 2 kScanChunk and of M^kScanSeg (segment_growth, stationary_common.h, shared with
+// sampler.hip; the smoother's figure also covers its G, which no forecast uses: it is not consulted), held against scan_growth_bound<Ta>().
 #include "scan_sweep.h"
 
 namespace moihgp {
@@ -78,7 +78,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(sizeof(
             if (regular) {   // a whole chunk without missing ticks: fixed trip count, no selects
 #pragma unroll
                 for (int i = 0; i < kScanChunk; i++) {
-                    Ta xm[D];
+                    Ta xm[D];   // (tick_step's loop, kept here: through the helper the fp32 sweeps come out rescheduled)
                     matvec<Ta, D>(M, xs, xm);
                     const Ta y = my[i];
 #pragma unroll
@@ -279,9 +279,7 @@ __global__ void __launch_bounds__(64) forecast_tables_kernel(int kernel, const d
     double M[NN], Kg[D], Mp[NN], MF[NN];
     for (int i = 0; i < NN; i++) M[i] = gains == 0 ? s[S::AKHA + i] : cb[C::AKHA + i];
     for (int i = 0; i < D; i++) Kg[i] = gains == 0 ? s[S::K + i] : cb[C::K + i];
-    double growth = chunk_powers<D, kScanChunk>(M, MF, Mp);   // Mp = M^(2 kScanChunk)
-    for (int q = 2 * kScanChunk; q < kScanSeg; q *= 2) mm<D>(Mp, Mp, Mp);   // M^kScanSeg: what one segment's scan composes
-    growth = fmax(growth, norm_inf<D>(Mp));
+    double growth = segment_growth<D, kScanChunk, kScanSeg>(M, MF, Mp);   // Mp = M^kScanSeg: what one segment's scan composes
     if (!isfinite(growth)) growth = INFINITY;              // (fmax drops a NaN operand: test the parts)
     for (int i = 0; i < NN; i++) if (!isfinite(Mp[i]) || !isfinite(MF[i])) growth = INFINITY;
     for (int i = 0; i < NN; i++) { put(B::A + i, A[i]); put(B::M + i, M[i]); put(B::MF + i, MF[i]); }

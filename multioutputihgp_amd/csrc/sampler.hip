@@ -20,7 +20,9 @@
 //   sample_serial_kernel    one lane per (latent, sample), tick by tick: the latents the sweep leaves (growth bound failed, option "sample_path"
 //                           = 1), the NaN rows of failed latents and every status word.
 //   sample_noise_kernel     the generator alone (moihgp_sample_noise), through the same sample_normals4.
-// Arithmetic is fp64 for both stream types (G exceeds the fp32 growth bound on ordinary parameters); the normals are formed in fp32.
+// Arithmetic is fp64 for both stream types (G exceeds the fp32 growth bound on ordinary parameters); the normals are formed in fp32.  The
+// chunk-scan machinery of the sweep is scan_sweep.h (its backward half, chunk_response_bwd and the mirrored scan, shared with smooth_bwd_kernel);
+// the Stein solve (stein_solve) and the growth figure (segment_growth) of the tables kernel are stationary_common.h's.
 #include "scan_sweep.h"
 #include <cstdint>
 
@@ -119,7 +121,7 @@ __global__ void __launch_bounds__(64) sample_sweep_kernel(const double* __restri
         __syncthreads();
         // this lane's ticks t0 .. t0 + n (the ragged tail is the identity: the state that enters the last segment is u[T-1])
         const size_t t0 = seg0 + (size_t)lane * kScanChunk;
-        const int n = t0 >= T ? 0 : (int)((T - t0) < (size_t)kScanChunk ? (T - t0) : (size_t)kScanChunk);
+        const int n = lane_tick_count(seg0, T, lane);
         double Pn[NN];                          // G^n, the same for every sample
         if (n == kScanChunk) {
 #pragma unroll
@@ -147,15 +149,7 @@ __global__ void __launch_bounds__(64) sample_sweep_kernel(const double* __restri
             double Phi[NN], r[D], u[D], useg[D];
 #pragma unroll
             for (int i = 0; i < NN; i++) Phi[i] = Pn[i];
-#pragma unroll
-            for (int i = 0; i < D; i++) r[i] = 0.0;
-            for (int i = kScanChunk - 1; i >= 0; i--) {
-                double rn[D];
-                matvec<double, D>(G, r, rn);
-                const double e = mo[i];
-#pragma unroll
-                for (int j = 0; j < D; j++) r[j] = fma(Bv[j], e, rn[j]);
-            }
+            chunk_response_bwd<double, D>(mo, G, Bv, r);
             // 2. mirrored scan: the state entering this lane's chunk from the right
 #pragma unroll
             for (int i = 0; i < D; i++) useg[i] = carry[s * D + i];
@@ -168,10 +162,7 @@ __global__ void __launch_bounds__(64) sample_sweep_kernel(const double* __restri
             for (int i = n - 1; i >= 0; i--) {
                 const double e = mo[i];
                 mo[i] = my[i] + (u[0] + e);
-                double un[D];
-                matvec<double, D>(G, u, un);
-#pragma unroll
-                for (int j = 0; j < D; j++) u[j] = fma(Bv[j], e, un[j]);
+                tick_step<double, D>(G, Bv, e, u);
             }
             __syncthreads();
             stage_out(ob, samples + (size_t)(s0 + s) * plane_stride + l * ld_out, seg0, T, lane);
@@ -217,9 +208,7 @@ __global__ void __launch_bounds__(64) sample_serial_kernel(const double* __restr
         if (k == 3 || t == T - 1) sample_normals4(seed, (uint32_t)(t >> 2), lat, smp, 0u, nz);
         const double e = sigma * (double)(k == 0 ? nz[0] : k == 1 ? nz[1] : k == 2 ? nz[2] : nz[3]);
         row[t] = (Tv)((double)yrow[t] + (u[0] + e));
-        double un[D];
-        matvec<double, D>(G, u, un);
-        for (int j = 0; j < D; j++) u[j] = fma(Bv[j], e, un[j]);
+        tick_step<double, D>(G, Bv, e, u);
     }
 }
 
@@ -251,24 +240,6 @@ __global__ void __launch_bounds__(256) sample_noise_kernel(unsigned long long se
 
 namespace moihgp {
 namespace {
-
-// S = sym(X) with X = Ac X Ac^T + RHS (exact d^2 x d^2 solve; the smoother's tables kernel keeps its own copy of this in smoother.hip)
-template <int D>
-__device__ __forceinline__ void sampler_stein_solve(const double* Ac, const double* RHS, double* S) {
-    constexpr int NN = D * D, N2 = NN * NN;
-    double M[N2], rhs[N2], sol[N2];
-    for (int i = 0; i < N2; i++) { M[i] = 0.0; rhs[i] = 0.0; }
-    for (int i = 0; i < D; i++)
-        for (int j = 0; j < D; j++) {
-            const int row = i * D + j;
-            rhs[row * NN] = RHS[row];
-            for (int k = 0; k < D; k++)
-                for (int m = 0; m < D; m++) M[row * NN + k * D + m] = (row == k * D + m ? 1.0 : 0.0) - Ac[i * D + k] * Ac[j * D + m];
-        }
-    lu_solve<NN>(M, rhs, sol);
-    for (int i = 0; i < D; i++)
-        for (int j = 0; j < D; j++) S[i * D + j] = (sol[(i * D + j) * NN] + sol[(j * D + i) * NN]) / 2.0;
-}
 
 template <int D>
 __global__ void __launch_bounds__(64) sampler_tables_kernel(const double* __restrict__ sm, size_t L, double* __restrict__ sp) {
@@ -315,7 +286,7 @@ __global__ void __launch_bounds__(64) sampler_tables_kernel(const double* __rest
         double Ac[NN], dS[NN];
         for (int i = 0; i < NN; i++) Ac[i] = G[i];
         for (int i = 0; i < D; i++) Ac[i * D] -= Bv[i];
-        sampler_stein_solve<D>(Ac, F, dS);
+        stein_solve<D>(Ac, F, dS);
         bool fin = true;
         for (int i = 0; i < NN; i++) fin = fin && isfinite(dS[i]);
         if (!fin) break;
@@ -356,9 +327,7 @@ __global__ void __launch_bounds__(64) sampler_tables_kernel(const double* __rest
     }
     for (int i = 0; i < NN; i++) ok = ok && isfinite(Lc[i]);
     // growth of the sweep's maps: G^1 .. G^(2 kScanChunk), and what a whole segment composes, G^kScanSeg
-    double growth = chunk_powers<D, kScanChunk>(G, T1, T2);
-    for (int p = 2 * kScanChunk; p < kScanSeg; p *= 2) mm<D>(T2, T2, T2);
-    growth = fmax(growth, norm_inf<D>(T2));
+    const double growth = segment_growth<D, kScanChunk, kScanSeg>(G, T1, T2);
     for (int i = 0; i < NN; i++) ok = ok && isfinite(T2[i]);
     for (int i = 0; i < NN; i++) { o[BP::LC + i] = Lc[i]; o[BP::SG + i] = Sg[i]; }
     for (int i = 0; i < D; i++) o[BP::B + i] = Bv[i];

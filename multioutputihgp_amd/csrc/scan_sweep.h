@@ -1,8 +1,10 @@
 // scan_sweep.h -- device machinery of the chunk-scan sweeps over whole streams (smoother.hip: smooth_fwd_kernel, smooth_bwd_kernel;
-// forecast.hip: forecast_sweep_kernel).  One wavefront per latent walks the stream in segments of 64 x kScanChunk ticks staged through LDS
-// (coalesced in and out): each lane takes kScanChunk consecutive ticks, computes its chunk's affine map from a zero state, a Kogge-Stone scan of
-// the maps over the 64 lanes gives every lane its true start state, and the lane replays its chunk from there.  What a sweep does in its replay
-// stays in its kernel.  Ta: the arithmetic (the smoother's double, the forecasts' stream scalar); D: the state dimension.
+// forecast.hip: forecast_sweep_kernel; sampler.hip: sample_sweep_kernel).  One wavefront per latent walks the stream in segments of
+// 64 x kScanChunk ticks staged through LDS (coalesced in and out): each lane takes kScanChunk consecutive ticks, computes its chunk's affine map
+// from a zero state, a Kogge-Stone scan of the maps over the 64 lanes gives every lane its true start state, and the lane replays its chunk from
+// there.  Both directions live here: forward in time (chunk_map, lane 0 first) and backward (chunk_response_bwd, lane 63 first, a chunk walked
+// from its last tick to its first); scan_maps and start_states take the direction as FWD.  What a sweep does in its replay stays in its kernel.
+// Ta: the arithmetic (the smoother's and the sampler's double, the forecasts' stream scalar); D: the state dimension.
 #pragma once
 #include "kernels_common.h"
 #include "stream_tables.h"
@@ -42,6 +44,15 @@ __device__ __forceinline__ void matvec(const Ta* M, const Ta* x, Ta* y) {
     matvec_acc<Ta, D>(M, x, y);
 }
 
+// one tick x <- M x + K e (the backward sweeps and the serial kernels; the forward chunk maps and replays keep their loops)
+template <typename Ta, int D>
+__device__ __forceinline__ void tick_step(const Ta* M, const Ta* K, Ta e, Ta* x) {
+    Ta xn[D];
+    matvec<Ta, D>(M, x, xn);
+#pragma unroll
+    for (int j = 0; j < D; j++) x[j] = fma(K[j], e, xn[j]);
+}
+
 // ---- segment staging ------------------------------------------------------------------------------------------------------------------------
 // Tick seg0 + tl of a segment (tl = k*64 + lane in a coalesced walk, k < kScanChunk) belongs to lane tl / kScanChunk's row of a staged plane
 __device__ __forceinline__ int scan_slot(int tl) { return (tl / kScanChunk) * kScanPitch + tl % kScanChunk; }
@@ -68,11 +79,15 @@ __device__ __forceinline__ void stage_out(const Ta* plane, Tv* row, size_t seg0,
     }
 }
 
-// valid ticks of this lane's chunk my[]; regular: a whole chunk without missing ticks
+// ticks of this lane's chunk that lie inside the stream
+__device__ __forceinline__ int lane_tick_count(size_t seg0, size_t T, int lane) {
+    const size_t t0 = seg0 + (size_t)lane * kScanChunk;
+    return t0 >= T ? 0 : (int)((T - t0) < (size_t)kScanChunk ? (T - t0) : (size_t)kScanChunk);
+}
+// ... of this lane's chunk my[]; regular: a whole chunk without missing ticks
 template <typename Ta>
 __device__ __forceinline__ int lane_ticks(const Ta* my, size_t seg0, size_t T, int lane, bool& regular) {
-    const size_t t0 = seg0 + (size_t)lane * kScanChunk;
-    const int n = t0 >= T ? 0 : (int)((T - t0) < (size_t)kScanChunk ? (T - t0) : (size_t)kScanChunk);
+    const int n = lane_tick_count(seg0, T, lane);
     regular = n == kScanChunk;
     for (int i = 0; i < n; i++) regular &= !isnan(my[i]);
     return n;
@@ -89,7 +104,7 @@ __device__ __forceinline__ void chunk_map(const Ta* y, int n, bool regular, cons
     if (regular) {
 #pragma unroll
         for (int i = 0; i < NN; i++) Phi[i] = MF[i];
-        for (int i = 0; i < kScanChunk; i++) {
+        for (int i = 0; i < kScanChunk; i++) {   // (tick_step's loop, kept here: through the helper the forecasts' fp32 sweeps come out rescheduled)
             Ta rn[D];
             matvec<Ta, D>(M, r, rn);
             const Ta yi = y[i];
@@ -112,6 +127,16 @@ __device__ __forceinline__ void chunk_map(const Ta* y, int n, bool regular, cons
             for (int j = 0; j < NN; j++) Phi[j] = Pn[j];
         }
     }
+}
+
+// Backward: the response r of the whole chunk e[0 .. kScanChunk) under s <- G s + K e[i], walked from its last tick to its first from a zero
+// state at its end (the recursion is time-invariant, so the chunk's map is a power of G that the caller holds; entries past the stream's end
+// are zero, come first and leave the state zero)
+template <typename Ta, int D>
+__device__ __forceinline__ void chunk_response_bwd(const Ta* e, const Ta* G, const Ta* K, Ta* r) {
+#pragma unroll
+    for (int i = 0; i < D; i++) r[i] = 0;
+    for (int i = kScanChunk - 1; i >= 0; i--) tick_step<Ta, D>(G, K, e[i], r);
 }
 
 // Inclusive Kogge-Stone scan of affine maps (Phi, r) over the wavefront.  FWD: lane j ends with the composition of lanes 0..j (lane 0 first);

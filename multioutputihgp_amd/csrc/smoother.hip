@@ -24,7 +24,8 @@
 //                            "smoother_path" = 1), and the status word of every latent.  The NaN row of a latent whose DARE did not converge
 //                            is written by smooth_fwd_kernel (by this kernel when it walks every latent).
 // Arithmetic is fp64 throughout; fp32 streams are widened on load and narrowed on store.  The chunk-scan machinery of the two sweep kernels is
-// scan_sweep.h (shared with forecast.hip), the block layout SM<D> stream_tables.h.
+// scan_sweep.h (shared with forecast.hip and sampler.hip; the backward chunk response is its chunk_response_bwd), the block layout SM<D>
+// stream_tables.h, the Stein solve (stein_solve) and the chunk powers of the tables kernel stationary_common.h.
 #include "scan_sweep.h"
 
 namespace moihgp {
@@ -122,25 +123,13 @@ __global__ void __launch_bounds__(64) smooth_bwd_kernel(const Tv* __restrict__ T
         double Phi[NN], r[D], s[D];
 #pragma unroll
         for (int i = 0; i < NN; i++) Phi[i] = MB[i];
-#pragma unroll
-        for (int i = 0; i < D; i++) r[i] = 0.0;
-        for (int i = kScanChunk - 1; i >= 0; i--) {
-            double rn[D];
-            matvec<double, D>(G, r, rn);
-            const double vi = v[i];
-#pragma unroll
-            for (int j = 0; j < D; j++) r[j] = fma(K[j], vi, rn[j]);
-        }
+        chunk_response_bwd<double, D>(v, G, K, r);
         // 2. mirrored scan: the state entering this lane's chunk from the right
         scan_maps<double, D, false>(Phi, r, lane);
         start_states<double, D, false>(Phi, r, sseg, s, lane);
         // 3. replay: ys = p + s_0 (in place of p)
         for (int i = kScanChunk - 1; i >= 0; i--) {
-            double sn[D];
-            matvec<double, D>(G, s, sn);
-            const double vi = v[i];
-#pragma unroll
-            for (int j = 0; j < D; j++) s[j] = fma(K[j], vi, sn[j]);
+            tick_step<double, D>(G, K, v[i], s);
             pw[i] += s[0];
         }
         __syncthreads();
@@ -181,9 +170,7 @@ __global__ void __launch_bounds__(64) smooth_serial_kernel(const Tv* __restrict_
     for (size_t t = T; t-- > 0;) {
         const double y = (double)yrow[t], p = (double)prow[t];
         const double v = isnan(y) ? 0.0 : y - p;
-        double sn[D];
-        matvec<double, D>(G, s, sn);
-        for (int j = 0; j < D; j++) s[j] = fma(K[j], v, sn[j]);
+        tick_step<double, D>(G, K, v, s);
         prow[t] = (Tv)(p + s[0]);
     }
 }
@@ -197,31 +184,6 @@ __global__ void __launch_bounds__(64) smooth_serial_kernel(const Tv* __restrict_
 
 namespace moihgp {
 namespace {
-
-template <int D>
-__device__ double max_abs(const double* X) {
-    double m = 0.0;
-    for (int i = 0; i < D * D; i++) m = fmax(m, fabs(X[i]));
-    return m;
-}
-// S = sym(X) with (I - Ac (x) Ac) vec(X) = vec(RHS), row-major vec: the solution of the Stein equation X = Ac X Ac^T + RHS (exact d^2 x d^2 solve).
-// (forceinline: inlined after it was optimised on its own, it costs smoother_tables_kernel<2> a wave per SIMD)
-template <int D>
-__device__ __forceinline__ void stein_solve(const double* Ac, const double* RHS, double* S) {
-    constexpr int NN = D * D, N2 = NN * NN;
-    double M[N2], rhs[N2], sol[N2];
-    for (int i = 0; i < N2; i++) { M[i] = 0.0; rhs[i] = 0.0; }
-    for (int i = 0; i < D; i++)
-        for (int j = 0; j < D; j++) {
-            const int row = i * D + j;
-            rhs[row * NN] = RHS[row];
-            for (int k = 0; k < D; k++)
-                for (int m = 0; m < D; m++) M[row * NN + k * D + m] = (row == k * D + m ? 1.0 : 0.0) - Ac[i * D + k] * Ac[j * D + m];
-        }
-    lu_solve<NN>(M, rhs, sol);
-    for (int i = 0; i < D; i++)
-        for (int j = 0; j < D; j++) S[i * D + j] = (sol[(i * D + j) * NN] + sol[(j * D + i) * NN]) / 2.0;
-}
 
 template <int D>
 __global__ void __launch_bounds__(64) smoother_tables_kernel(int kernel, const double* __restrict__ cb64, size_t L, double* __restrict__ tabs) {

@@ -1,5 +1,6 @@
-// stationary_common.h -- small dense helpers shared by stationary.hip and stationary_x.hip (one lane per latent, fp64):
-// matrix products, Eigen-style Pade matrix exponential, and the literal fixed-point solvers of the reference's utils/dare.h.
+// stationary_common.h -- small dense helpers shared by stationary.hip, stationary_x.hip and the tables kernels of smoother.hip, forecast.hip and
+// sampler.hip (one lane per latent, fp64): matrix products, chunk powers and growth figures, the LU and Stein solves, Eigen-style Pade matrix
+// exponential, and the literal fixed-point solvers of the reference's utils/dare.h.
 // Include AFTER `#pragma clang fp contract(off)`: the iteration counts of DARE/DLyap must agree with a plain-C evaluation.
 #pragma once
 #include "common.h"
@@ -58,6 +59,14 @@ __device__ inline double chunk_powers(const double* X, double* Xc, double* Xp) {
         if (p == 2 * C) return growth;
         mm<N>(X, Xp, Xp);
     }
+}
+// The growth figure of a whole segment of SEG ticks walked in chunks of C: Xc <- X^C, Xs <- X^SEG (SEG = 2C times a power of two); returns the
+// largest inf-norm of X^1 .. X^(2C) and of X^SEG (NaN operands drop out as in chunk_powers: the caller tests Xc and Xs)
+template <int N, int C, int SEG>
+__device__ inline double segment_growth(const double* X, double* Xc, double* Xs) {
+    const double growth = chunk_powers<N, C>(X, Xc, Xs);
+    for (int p = 2 * C; p < SEG; p *= 2) mm<N>(Xs, Xs, Xs);
+    return fmax(growth, norm_inf<N>(Xs));
 }
 template <int N>
 __device__ inline bool all_zero(const double* A) {
@@ -140,6 +149,31 @@ __device__ void lu_solve(const double* Ain, const double* Bin, double* X) {
             for (int k = i + 1; k < N; k++) s -= A[i * N + k] * X[k * N + j];
             X[i * N + j] = s / A[i * N + i];
         }
+}
+
+template <int D>
+__device__ double max_abs(const double* X) {
+    double m = 0.0;
+    for (int i = 0; i < D * D; i++) m = fmax(m, fabs(X[i]));
+    return m;
+}
+// S = sym(X) with (I - Ac (x) Ac) vec(X) = vec(RHS), row-major vec: the solution of the Stein equation X = Ac X Ac^T + RHS (exact d^2 x d^2 solve).
+// (forceinline: inlined after it was optimised on its own, it costs smoother_tables_kernel<2> a wave per SIMD)
+template <int D>
+__device__ __forceinline__ void stein_solve(const double* Ac, const double* RHS, double* S) {
+    constexpr int NN = D * D, N2 = NN * NN;
+    double M[N2], rhs[N2], sol[N2];
+    for (int i = 0; i < N2; i++) { M[i] = 0.0; rhs[i] = 0.0; }
+    for (int i = 0; i < D; i++)
+        for (int j = 0; j < D; j++) {
+            const int row = i * D + j;
+            rhs[row * NN] = RHS[row];
+            for (int k = 0; k < D; k++)
+                for (int m = 0; m < D; m++) M[row * NN + k * D + m] = (row == k * D + m ? 1.0 : 0.0) - Ac[i * D + k] * Ac[j * D + m];
+        }
+    lu_solve<NN>(M, rhs, sol);
+    for (int i = 0; i < D; i++)
+        for (int j = 0; j < D; j++) S[i * D + j] = (sol[(i * D + j) * NN] + sol[(j * D + i) * NN]) / 2.0;
 }
 
 // E = exp(Ain): Pade approximant of degree 3/5/7/9/13 by 1-norm, scaling & squaring for the last.

@@ -108,9 +108,9 @@ def _forecast_gains(gains) -> int:
     return _GAINS[gains]
 
 
-def _forecast_out_strides(out: torch.Tensor, K: int, L: int, T: int, Ty: torch.Tensor):
-    """(ld_out, plane_stride) of a forecast buffer [K, L, >=T] for the stream Ty, or ValueError: dtype, device, shape, unit stride along time, row and
-    plane strides multiples of 16 bytes, rows >= T rounded up, planes >= L rows, and no overlap with Ty."""
+def _plane_out_strides(out: torch.Tensor, K: int, L: int, T: int, Ty: torch.Tensor):
+    """(ld_out, plane_stride) of a buffer of K planes [K, L, >=T] (forecast horizons, posterior samples) for the stream Ty, or ValueError:
+    dtype, device, shape, unit stride along time, row and plane strides multiples of 16 bytes, rows >= T rounded up, planes >= L rows, and no overlap with Ty."""
     epv = 2 if Ty.dtype == torch.float64 else 4
     ok = (out.device == Ty.device and out.dtype == Ty.dtype and out.dim() == 3 and out.shape[0] == K and out.shape[1] == L and out.shape[2] >= T
           and (out.shape[2] <= 1 or out.stride(2) == 1) and out.data_ptr() % 16 == 0)
@@ -391,7 +391,7 @@ class LatentBank:
         if out is None:
             ysmooth, ld_out = self._ysmooth_buffer(Ty, T, ysmooth)
             out = torch.empty((S, self.L, ld_out), dtype=Ty.dtype, device=Ty.device)[:, :, :T]
-        ld_out, plane = _forecast_out_strides(out, S, self.L, T, Ty)
+        ld_out, plane = _plane_out_strides(out, S, self.L, T, Ty)
         # one row stride serves both buffers in the C entry: means without a buffer of their own take the sample planes' stride, and a caller's
         # `ysmooth` of another stride receives a copy
         ys_user = None
@@ -441,7 +441,7 @@ class LatentBank:
         x, start = self._start_state(Ty, x, x_start)
         if out is None:
             out = torch.empty((K, self.L, padded_len(max(T, 1), Ty.dtype)), dtype=Ty.dtype, device=Ty.device)[:, :, :T]
-        ld_out, plane = _forecast_out_strides(out, K, self.L, T, Ty)
+        ld_out, plane = _plane_out_strides(out, K, self.L, T, Ty)
         status = torch.empty((self.L,), dtype=torch.int32, device=Ty.device)
         rc = self._lib.moihgp_forecast_stream(self._h, _DT[Ty.dtype], C.c_void_p(Ty.data_ptr()), T, ld,
                                               C.c_void_p(start.data_ptr()), C.c_void_p(x.data_ptr()), hz, K,

@@ -176,7 +176,7 @@ def test_python_argument_validation():
     slab = torch.zeros(8 * L * 112, dtype=torch.float64)
     Ty = slab[:L * 104].view(L, 104)[:, :T]
     good = torch.as_strided(slab, (2, L, T), (L * 108 + 4, 108, 1), L * 104)
-    assert streams._forecast_out_strides(good, 2, L, T, Ty) == (108, L * 108 + 4)
+    assert streams._plane_out_strides(good, 2, L, T, Ty) == (108, L * 108 + 4)
     bads = [torch.as_strided(slab, (2, L, T), (L * 108 + 4, 108, 1), 8),             # overlaps Ty
             torch.as_strided(slab, (2, L, T), (L * 108 + 4, 107, 1), L * 104),       # row stride not a multiple of 16 bytes
             torch.as_strided(slab, (2, L, T), (L * 108 + 1, 108, 1), L * 104),       # plane stride not a multiple of 16 bytes
@@ -189,7 +189,7 @@ def test_python_argument_validation():
             torch.zeros((2, L, 108), dtype=torch.float32)[:, :, :T]]                 # dtype
     for b in bads:
         with pytest.raises(ValueError):
-            streams._forecast_out_strides(b, 2, L, T, Ty)
+            streams._plane_out_strides(b, 2, L, T, Ty)
 
 
 # ------------------------------------------------------------------------------------------------ GPU

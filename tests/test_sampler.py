@@ -390,6 +390,60 @@ def test_sample_ranges_reproduce_one_call(env, dtype, path):
     assert not torch.equal(whole, bank.sample(dev, 4, seed=SEED + 1)[0])
 
 
+# ------------------------------------------------------------------------------------------------ GPU: the lazy tables
+@pytest.mark.gpu
+@pytest.mark.parametrize("first", ["sample", "read"])
+def test_sample_after_update_uses_the_new_parameters(env, first):
+    """The realization's tables follow a parameter update, whether a sweep or a host read built them before it."""
+    torch, streams = env["torch"], env["streams"]
+    L, T, S = 7, 1000, 3
+    bank, _, _ = bank_and_tables(streams, "Matern52", L)
+    dev = to_dev(torch, synth(L, T, np.random.default_rng(29)), torch.float64, T)
+    if first == "sample":
+        bank.sample(dev, S, seed=SEED)
+    else:
+        bank.sampler(0)
+    pool2 = [(p[0] * 1.5, p[1] * 0.7, p[2] * 2.0) for p in POOL]      # of test_smooth_after_update_uses_the_new_parameters
+    bank.update(np.array([pool2[l % len(pool2)] for l in range(L)]))
+    smp, ys, _, status = bank.sample(dev, S, seed=SEED)
+    torch.cuda.synchronize()
+    assert not status.cpu().numpy().any()
+    for l in range(L):
+        tb = tables("Matern52", 0.1, pool2[l % len(pool2)])
+        got, ref = bank.sampler(l), realization(tb["G"], tb["Ps"])
+        assert got["status"] == 0 and got["acov_err"] <= 1e-9, (l, got)
+        assert rel_err(got["B"], ref["B"]) <= 1e-8 and abs(got["sigma2"] - ref["sigma2"]) <= 1e-8 * ref["sigma2"], (l, got, ref)
+    assert worst_row(smp.cpu().numpy(), reference_samples(streams, bank, L, S, T, ys)) <= TOL["f64"]
+
+
+@pytest.mark.gpu
+def test_tables_built_on_one_stream_serve_another(env):
+    """The smoother's tables are built on s1 and read on s2, the realization's built on s2 and read on s1: every call gives what the same calls
+    on one stream of another fresh bank give.  (One run cannot prove the ordering; it pins the contract and catches an event that is not
+    recorded or not waited for.)"""
+    torch, streams = env["torch"], env["streams"]
+    L, T, S, hz = 8, 1500, 3, (1, 7)
+    dev = to_dev(torch, synth(L, T, np.random.default_rng(30)), torch.float64, T)
+    torch.cuda.synchronize()
+
+    def calls(s1, s2):
+        bank, _, _ = bank_and_tables(streams, "Matern52", L)
+        with torch.cuda.stream(s1):
+            out = list(bank.smooth(dev))
+        with torch.cuda.stream(s2):
+            out += list(bank.sample(dev, S, seed=SEED)) + list(bank.forecast(dev, hz, gains="kalman"))
+        with torch.cuda.stream(s1):
+            out += list(bank.sample(dev, S, seed=SEED))
+        s1.synchronize(); s2.synchronize()
+        return out
+
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    two, one = calls(s1, s2), calls(s1, s1)
+    assert len(two) == len(one) == 14
+    for i, (a, b) in enumerate(zip(two, one)):
+        assert torch.equal(a, b), i
+
+
 # ------------------------------------------------------------------------------------------------ GPU: status
 @pytest.mark.gpu
 @pytest.mark.parametrize("path", [-1, 0, 1])
