@@ -57,20 +57,23 @@ def to_dev(a, dtype):
 @pytest.mark.parametrize("kern", ["Matern32", "Matern52"])
 def test_stationary_matrices_vs_golden(env, kern):
     g = load_golden(f"stationary_{kern}.npz")
-    same_dt = np.isclose(g["dt"], 0.1)
-    bank = env["streams"].LatentBank(0.1, g["params"][same_dt], kernel=KMAP[kern])
-    worst = 0.0
-    for j, i in enumerate(np.nonzero(same_dt)[0]):
-        lat = bank.latent(j)
-        for k in ("A", "K", "HA", "AKHA", "dA", "dS", "dK", "dAKHA", "HdA"):
-            ref = g[k][i]
-            if np.max(np.abs(ref)) == 0:
-                assert np.max(np.abs(lat[k])) == 0
-            else:
-                e = rel_err(lat[k], ref); worst = max(worst, e)
-                assert e < FP64_TIGHT, (k, i, e)
-        assert abs(lat["S"] - g["S"][i]) / g["S"][i] < FP64_TIGHT
-        assert lat["iters"] == list(g["iters"][i])     # DARE / DLyap iteration counts (utils/dare.h)
+    worst, seen = 0.0, 0
+    for dt in np.unique(g["dt"]):                          # one bank per time step of the file: every row is compared
+        same_dt = g["dt"] == dt
+        bank = env["streams"].LatentBank(float(dt), g["params"][same_dt], kernel=KMAP[kern])
+        for j, i in enumerate(np.nonzero(same_dt)[0]):
+            lat = bank.latent(j)
+            for k in ("A", "K", "HA", "AKHA", "dA", "dS", "dK", "dAKHA", "HdA"):
+                ref = g[k][i]
+                if np.max(np.abs(ref)) == 0:
+                    assert np.max(np.abs(lat[k])) == 0
+                else:
+                    e = rel_err(lat[k], ref); worst = max(worst, e)
+                    assert e < FP64_TIGHT, (k, i, e)
+            assert abs(lat["S"] - g["S"][i]) / g["S"][i] < FP64_TIGHT
+            assert lat["iters"] == list(g["iters"][i])     # DARE / DLyap iteration counts (utils/dare.h)
+            seen += 1
+    assert seen == len(g["dt"])
     print(f"stationary {kern}: worst rel err {worst:.2e}")
 
 
