@@ -765,9 +765,14 @@ int moihgp_get_latent(moihgp_gp* gp, size_t l, double* A, double* K, double* S, 
     return guard_rc([&] { return get_latent_impl(gp, l, A, K, S, HA, AKHA, dA, dS, dK, dAKHA, HdA, iters); });
 }
 
-static int check_stream_args(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld, const void* x) {
+static int check_handle_dtype(moihgp_gp* gp, int dtype) {
     if (!gp) { set_last_error("null handle"); return 1; }
     if (dtype != MOIHGP_F64 && dtype != MOIHGP_F32) { set_last_error("dtype must be MOIHGP_F64 or MOIHGP_F32"); return 1; }
+    return 0;
+}
+
+static int check_stream_args(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld, const void* x) {
+    if (int rc = check_handle_dtype(gp, dtype)) return rc;
     const size_t es = dtype == MOIHGP_F64 ? 8 : 4, epv = 16 / es;
     if (!x || (T > 0 && !Ty)) { set_last_error("null stream/state pointer"); return 1; }
     if (((uintptr_t)Ty & 15) != 0) { set_last_error("stream base must be 16-byte aligned"); return 1; }
@@ -782,162 +787,191 @@ static int check_sweep_call(moihgp_gp* gp, int dtype, const void* Ty, size_t T, 
     return 0;
 }
 
+static int check_nll_total(const double* nll_total, const double* nll) {
+    if (nll_total && !nll) { set_last_error("nll_total needs the per-latent nll buffer"); return 1; }
+    return 0;
+}
+
 int moihgp_filter_stream(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld, void* x, void* yhat, double* nll, void* stream) {
     return moihgp_filter_stream_io(gp, dtype, Ty, T, ld, x, x, yhat, nll, nullptr, stream);
 }
 
-// Which sweeps of the reference's own models go through the stacked filter's kernels when nobody says (option filter_plain_x = -1).
-static bool plain_x_by_default(int d, int dtype, size_t L, size_t T) {
-    (void)d; (void)dtype; (void)L; (void)T;
-    return false;
-}
-
-static int filter_stream_io_impl(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld, const void* x_in, void* x, void* yhat, double* nll,
-                            double* nll_total, void* stream, size_t ld_out = 0) {
-    if (int rc = check_stream_args(gp, dtype, Ty, T, ld, x)) return rc;
-    if (!x_in) { set_last_error("null start state"); return 1; }
-    note_user_stream(gp, (hipStream_t)stream);
-    if (nll_total && !nll) { set_last_error("nll_total needs the per-latent nll buffer"); return 1; }
-    if (nll_total && T == 0) MOIHGP_HIP_FATAL(hipMemsetAsync(nll_total, 0, sizeof(double), (hipStream_t)stream));
-    if (yhat && ((uintptr_t)yhat & 15) != 0) { set_last_error("yhat base must be 16-byte aligned"); return 1; }
-    if (ld_out == 0) ld_out = ld;
-    {
-        const size_t epv = dtype == MOIHGP_F64 ? 2 : 4;
-        if (yhat && (ld_out % epv != 0 || ld_out < (T + epv - 1) / epv * epv)) {
-            set_last_error("ld_out (%zu) must be a multiple of %zu and >= T rounded up to it", ld_out, epv);
-            return 1;
-        }
-    }
-    const int variant = gp->opt_filter_variant;              // tuning probes: only a -DMOIHGP_TUNING build accepts a non-zero value
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+// The next profile event pair for this sweep's kernel, where profiling is on and the sweep is one of those it samples (moihgp_profile_enable / _stride).
+static void claim_profile_events(moihgp_gp* gp, SweepIo& io) {
     if (!gp->prof_ev.empty() && 2 * (size_t)(gp->prof_n + 1) <= gp->prof_ev.size() && (gp->prof_seen++ % gp->prof_stride) == 0) {
-        e0 = gp->prof_ev[2 * gp->prof_n];
-        e1 = gp->prof_ev[2 * gp->prof_n + 1];
+        io.ev0 = gp->prof_ev[2 * gp->prof_n];
+        io.ev1 = gp->prof_ev[2 * gp->prof_n + 1];
         gp->prof_n++;
     }
-    // the reference's own models through the stacked filter's kernels (one component; tables from launch_xc_from_cb)
-    const bool plain_x = !kernel_stack(gp->kernel) && gp->dxc64 && variant == 0 && gp->opt_filter_split == 0 &&
-                         (gp->opt_filter_plain_x == 1 || (gp->opt_filter_plain_x == -1 && plain_x_by_default(gp->d, dtype, gp->L, T)));
-    if (kernel_stack(gp->kernel) || plain_x) {
-        const int kid = plain_x ? (gp->kernel | (1 << 4)) : gp->kernel;
-        const double* xb64 = plain_x ? gp->dxc64 : gp->cb64;
-        const float* xb32 = plain_x ? gp->dxc32 : gp->cb32;
-        const size_t slen = gp->L < 1024 ? gp->L * 16 : 0;              // per-slice NLL partials of the time split (few latents only)
-        if (slen && !gp->dxscratch) gp->dxscratch = dev_alloc<double>(slen);
-        if (gp->L >= 1024 && !gp->dlink) {                                               // hand-over records and flags of the second (broken-link) pass
-            gp->dlink = dev_alloc<double>(gp->L * 144);
-            gp->dlinkflags = dev_alloc<int>(gp->L);
-            MOIHGP_HIP_FATAL(hipMemsetAsync(gp->dlinkflags, 0, gp->L * sizeof(int), (hipStream_t)stream));
-        }
-        // fp32 streams, many latents: the latents whose fp32 scan tables are unusable while the fp64 ones are fine (a mildly unstable filter; listed at
-        // update(), skipped by the many-latent kernel) are swept in fp64 on the handle's own stream, beside the sweep -- tick by tick in the fp32
-        // kernel one of them holds the whole launch (4096 x 10^4 Matern32x2: 7 such latents, 302 us against 80)
-        const size_t n_res = (!plain_x && dtype == MOIHGP_F32 && gp->L >= 1024 && T > 0) ? (size_t)gp->n_unstable[2] : 0;
-        if (n_res) {
-            const size_t xcs = (size_t)xc_size(gp->d), dd = (size_t)gp->d;
-            const size_t tpe = team_powers_elems(gp->d);
-            const size_t need = (2 * n_res * ld + 2 * n_res * dd + n_res + n_res * 16) * sizeof(double);
-            if (gp->rescue_cap < need) {
-                if (gp->drescue) { MOIHGP_HIP_FATAL(hipDeviceSynchronize()); MOIHGP_HIP_FATAL(hipFree(gp->drescue)); gp->drescue = nullptr; gp->rescue_cap = 0; }
-                MOIHGP_HIP_FATAL(hipMalloc(&gp->drescue, need));
-                gp->rescue_cap = need;
-            }
-            double* rin = static_cast<double*>(gp->drescue);
-            double* rout = rin + n_res * ld;
-            double* xi = rout + n_res * ld;
-            double* xo = xi + n_res * dd;
-            double* nc = xo + n_res * dd;
-            double* sc = nc + n_res;
-            double* cbc = static_cast<double*>(gp->drescue_const);        // (run_ihgp_update)
-            double* tpd = cbc + n_res * xcs;                              // the few-latents team kernel's scan powers: segments side by side, a fifth of the latency
-            float* tpf = reinterpret_cast<float*>(tpd + n_res * tpe);
-            if (const char* tr = getenv("MOIHGP_GAP_TRACE"); tr && tr[0] == '1') fprintf(stderr, "moihgp side sweep: %zu latents of the fp32 bank in fp64\n", n_res);
-            wait_for_caller(gp, (hipStream_t)stream);                    // (behind the caller's queue so far: the stream and the start states are there)
-            launch_rescue_gather(static_cast<const float*>(Ty), T, ld, gp->drescue_idx, n_res, nullptr, (int)xcs, static_cast<const float*>(x_in), gp->d, rin, nullptr, xi, gp->stream);
-            if (int rc = launch_filter_stream_x(kid, MOIHGP_F64, rin, T, ld, n_res, cbc, nullptr, xi, xo, yhat ? rout : nullptr, nll ? nc : nullptr, gp->stream, nullptr, nullptr,
-                                                sc, n_res * 16, 0, ld, nullptr, nullptr, nullptr, gp->opt_filter_maxlinks, -1, tpd, tpf)) return rc;
-            launch_rescue_scatter(gp->drescue_idx, n_res, rout, T, ld, xo, gp->d, nc, static_cast<float*>(yhat), ld_out, static_cast<float*>(x), nll, gp->stream);
-        }
-        auto rescued = [&]() {                                          // the caller's stream waits for the side sweep; the total over all latents
-            if (!n_res) return;
-            caller_waits(gp, (hipStream_t)stream);
-            if (nll && nll_total) launch_nll_total(nll, gp->L, nll_total, (hipStream_t)stream);
-        };
-        // many latents, a state too wide for per-chunk maps: latents whose stream holds missing ticks are swept by imputation (recursion_x.hip:
-        // filter_x_gaps_a / _b_kernel) between the first pass, which hands them over, and the second, which takes what the imputation could not.
-        // Left to itself: at d >= 8 always (the second pass alone is 4-6 x slower there), below it -- where the second pass scans the chunks' own
-        // maps -- only for a bank without slow filters, whose latents would take both (measured, tools/filternan.py, 4096 x 10^4 at 1 % missing:
-        // 2 x Matern-5/2 0.81 -> 0.45 ms; 2 x Matern-3/2 at the bench's draw, 13 % of them slow, 0.37 -> 0.63)
-        const bool impute = !plain_x && gp->L >= 1024 && T > 0 && gp->opt_filter_split == 0 && (yhat || nll) &&
-                            (gp->opt_filter_impute == 1 || (gp->opt_filter_impute == -1 && (gp->d >= 8 || gp->n_unstable[3] == 0)));
-        // (its scratch is 12 or 20 bytes per tick and latent -- the lists of gaps, sized for the worst case: beyond 16 GB (MOIHGP_GAP_BANK_GB) the stream
-        // is too long for one call's worth of it and the second pass alone takes the gaps, as before round 4; slabs of a long stream stay below)
-        static const size_t gap_bank_limit = []() { const char* e = getenv("MOIHGP_GAP_BANK_GB"); const double gb = e ? atof(e) : 16.0; return (size_t)(gb * 1073741824.0); }();
-        if (impute && gap_bank_bytes(gp->d, dtype, gp->L, T) <= gap_bank_limit) {
-            const size_t need = gap_bank_bytes(gp->d, dtype, gp->L, T);
-            if (gp->gap_cap < need) {
-                if (gp->dgap) { MOIHGP_HIP_FATAL(hipDeviceSynchronize()); MOIHGP_HIP_FATAL(hipFree(gp->dgap)); gp->dgap = nullptr; gp->gap_cap = 0; }
-                void* p = nullptr;
-                MOIHGP_HIP_FATAL(hipMalloc(&p, need));
-                gp->dgap = p; gp->gap_cap = need; gp->gap_sig = 0;
-            }
-            const GapBank bank = gap_bank_carve(gp->dgap, gp->d, dtype, gp->L, T);
-            const unsigned long long sig = (unsigned long long)(dtype + 1);
-            if (gp->gap_sig != sig) {                                    // a fresh bank, or another scalar type: unit impulses and the zero state again
-                if (int rc = gap_bank_init(bank, gp->d, dtype, gp->L, (hipStream_t)stream)) return rc;
-                gp->gap_sig = sig; gp->gap_imp_version = 0;
-            }
-            if (gp->gap_imp_version != gp->cb_version) {                 // the filters' impulse responses: once per parameter update
-                if (int rc = launch_gap_impulse(bank, kid, dtype, gp->L, xb64, xb32, (hipStream_t)stream)) return rc;
-                gp->gap_imp_version = gp->cb_version;
-            }
-            if (int rc = launch_filter_stream_x(kid, dtype, Ty, T, ld, gp->L, xb64, xb32, x_in, x, yhat, nll, (hipStream_t)stream, e0, e1, gp->dxscratch, slen, -2, ld_out,
-                                                gp->dlinkflags, gp->dlink, nullptr, gp->opt_filter_maxlinks, gp->opt_filter_team, gp->dtp64, gp->dtp32)) return rc;
-            const GapArgs ga{bank.imp_out, bank.gpos, bank.gval, bank.gw, bank.gcap, bank.gstat};
-            const char* trace = getenv("MOIHGP_GAP_TRACE");               // diagnostics (the tests read it): synchronises the stream
-            const bool tracing = trace && trace[0] == '1';
-            if (tracing) MOIHGP_HIP_FATAL(hipMemsetAsync(bank.gstat, 0xFF, gp->L * sizeof(int), (hipStream_t)stream));
-            if (int rc = launch_filter_stream_x(kid, dtype, Ty, T, ld, gp->L, xb64, xb32, x_in, x, yhat, nll, (hipStream_t)stream, nullptr, nullptr,
-                                                reinterpret_cast<double*>(const_cast<GapArgs*>(&ga)), 0, -7, ld_out, gp->dlinkflags, gp->dlink, nullptr, -1, 0, nullptr, nullptr)) return rc;
-            // what the recursion could not take (a filter with a memory longer than its table): the second pass, as without imputation
-            if (int rc = launch_filter_stream_x(kid, dtype, Ty, T, ld, gp->L, xb64, xb32, x_in, x, yhat, nll, (hipStream_t)stream, nullptr, nullptr, gp->dxscratch, slen, -3, ld_out,
-                                                gp->dlinkflags, gp->dlink, nullptr, gp->opt_filter_maxlinks, gp->opt_filter_team, gp->dtp64, gp->dtp32)) return rc;
-            if (n_res) rescued();
-            else if (nll && nll_total) launch_nll_total(nll, gp->L, nll_total, (hipStream_t)stream);
-            if (tracing) {
-                std::vector<int> st(gp->L);
-                MOIHGP_HIP_FATAL(hipMemcpyAsync(st.data(), bank.gstat, gp->L * sizeof(int), hipMemcpyDeviceToHost, (hipStream_t)stream));
-                MOIHGP_HIP_FATAL(hipStreamSynchronize((hipStream_t)stream));
-                long taken = 0, solved = 0, gaps = 0, states = 0, why[6] = {0, 0, 0, 0, 0, 0};
-                for (int v : st) if (v >= 0) {
-                    taken++;
-                    if (v & 1) { solved++; gaps += (v & 0x3FFFFFFF) >> 1; states += (v >> 30) & 1; } else why[(v >> 1) < 6 ? (v >> 1) : 0]++;
-                }
-                fprintf(stderr, "moihgp gap imputation: %ld latents handed over, %ld solved, %ld gaps filled (%ld of the latents by the state form: memory beyond the table or "
-                        "the ring; not solved: %ld response not finite or growing, %ld fill value not finite, %ld stream too long)\n", taken, solved, gaps, states, why[1], why[5], why[4]);
-            }
-            return 0;
-        }
-        int rc = launch_filter_stream_x(kid, dtype, Ty, T, ld, gp->L, xb64, xb32, x_in, x, yhat, nll, (hipStream_t)stream, e0, e1,
-                                        gp->dxscratch, slen, gp->opt_filter_split /* test hook: 1 = off, n = slices */, ld_out, gp->L >= 1024 ? gp->dlinkflags : nullptr, gp->dlink,
-                                        (nll && !n_res) ? nll_total : nullptr, gp->opt_filter_maxlinks, gp->opt_filter_team, gp->dtp64, gp->dtp32);
-        if (rc == 0) rescued();
-        return rc;
+}
+
+// A device buffer the handle keeps between calls, grown to at least `need` bytes (contents are not kept; the device is idle before the old one goes).
+// Returns true if the buffer is a new one.
+static bool grow_device_buffer(void*& buf, size_t& cap, size_t need) {
+    if (cap >= need) return false;
+    if (buf) { MOIHGP_HIP_FATAL(hipDeviceSynchronize()); MOIHGP_HIP_FATAL(hipFree(buf)); buf = nullptr; cap = 0; }
+    MOIHGP_HIP_FATAL(hipMalloc(&buf, need));
+    cap = need;
+    return true;
+}
+
+// ---- the routes of moihgp_filter_stream_io (filter_stream_io_impl picks one) ----
+// One call of the stacked filter's kernels: the model's kernel id and XC blocks, and what the handle holds for the stacked path.
+struct StackedCall {
+    int kid;
+    const double* cb64;
+    const float* cb32;
+    StackOpts opts;
+    size_t n_res;               // latents of an fp32 bank swept in fp64 on the side (rescue_side_sweep), whose results the caller's stream waits for
+};
+
+// fp32 streams, many latents: the latents whose fp32 scan tables are unusable while the fp64 ones are fine (a mildly unstable filter; listed at
+// update(), skipped by the many-latent kernel) are swept in fp64 on the handle's own stream, beside the sweep -- tick by tick in the fp32
+// kernel one of them holds the whole launch (4096 x 10^4 Matern32x2: 7 such latents, 302 us against 80)
+static int rescue_side_sweep(moihgp_gp* gp, const SweepIo& io, const StackedCall& c) {
+    const size_t n_res = c.n_res, T = io.T, ld = io.ld;
+    const size_t xcs = (size_t)xc_size(gp->d), dd = (size_t)gp->d;
+    const size_t tpe = team_powers_elems(gp->d);
+    grow_device_buffer(gp->drescue, gp->rescue_cap, (2 * n_res * ld + 2 * n_res * dd + n_res + n_res * 16) * sizeof(double));
+    double* rin = static_cast<double*>(gp->drescue);
+    double* rout = rin + n_res * ld;
+    double* xi = rout + n_res * ld;
+    double* xo = xi + n_res * dd;
+    double* nc = xo + n_res * dd;
+    double* sc = nc + n_res;
+    double* cbc = static_cast<double*>(gp->drescue_const);        // (run_ihgp_update)
+    double* tpd = cbc + n_res * xcs;                              // the few-latents team kernel's scan powers: segments side by side, a fifth of the latency
+    float* tpf = reinterpret_cast<float*>(tpd + n_res * tpe);
+    if (const char* tr = getenv("MOIHGP_GAP_TRACE"); tr && tr[0] == '1') fprintf(stderr, "moihgp side sweep: %zu latents of the fp32 bank in fp64\n", n_res);
+    wait_for_caller(gp, io.stream);                              // (behind the caller's queue so far: the stream and the start states are there)
+    launch_rescue_gather(static_cast<const float*>(io.Ty), T, ld, gp->drescue_idx, n_res, nullptr, (int)xcs, static_cast<const float*>(io.xin), gp->d, rin, nullptr, xi, gp->stream);
+    StackOpts opts;
+    opts.slice_nll = sc; opts.slice_nll_len = n_res * 16;
+    opts.max_links = gp->opt_filter_maxlinks;
+    opts.tp64 = tpd; opts.tp32 = tpf;
+    if (int rc = launch_filter_stream_x(c.kid, sweep_io(MOIHGP_F64, rin, T, ld, n_res, xi, xo, io.yhat ? rout : nullptr, ld, io.nll ? nc : nullptr, nullptr, gp->stream),
+                                        cbc, nullptr, opts)) return rc;
+    launch_rescue_scatter(gp->drescue_idx, n_res, rout, T, ld, xo, gp->d, nc, static_cast<float*>(io.yhat), io.ld_out, static_cast<float*>(io.x), io.nll, gp->stream);
+    return 0;
+}
+
+// ... after which the caller's stream waits for the side sweep; the total over all latents (the main sweep ran without one: StackedCall::n_res)
+static void join_rescue(moihgp_gp* gp, const SweepIo& io) {
+    caller_waits(gp, io.stream);
+    if (io.nll && io.total) launch_nll_total(io.nll, gp->L, io.total, io.stream);
+}
+
+// The sweep proper of the stacked path, in one call (first pass plus second, a team kernel or the time split: recursion_x.hip launch_xd).
+static int stacked_sweep(moihgp_gp* gp, const SweepIo& io, const StackedCall& c) {
+    SweepIo main = io;
+    if (c.n_res) main.total = nullptr;
+    StackOpts opts = c.opts;
+    opts.slices = gp->opt_filter_split;                              // test hook: 1 = off, n = slices
+    const int rc = launch_filter_stream_x(c.kid, main, c.cb64, c.cb32, opts);
+    if (rc == 0 && c.n_res) join_rescue(gp, io);
+    return rc;
+}
+
+// Many latents, a state too wide for per-chunk maps: latents whose stream holds missing ticks are swept by imputation (recursion_x.hip:
+// filter_x_gaps_a / _b_kernel) between the first pass, which hands them over, and the second, which takes what the imputation could not.
+static int imputation_sweeps(moihgp_gp* gp, const SweepIo& io, const StackedCall& c) {
+    const int dtype = io.dtype;
+    if (grow_device_buffer(gp->dgap, gp->gap_cap, gap_bank_bytes(gp->d, dtype, gp->L, io.T))) gp->gap_sig = 0;
+    const GapBank bank = gap_bank_carve(gp->dgap, gp->d, dtype, gp->L, io.T);
+    const unsigned long long sig = (unsigned long long)(dtype + 1);
+    if (gp->gap_sig != sig) {                                    // a fresh bank, or another scalar type: unit impulses and the zero state again
+        if (int rc = gap_bank_init(bank, gp->d, dtype, gp->L, io.stream)) return rc;
+        gp->gap_sig = sig; gp->gap_imp_version = 0;
     }
-    // few latents, streams of 2 .. 8 segments: one workgroup per latent, eight wavefronts (the stacked filter's team kernel, recursion_x.hip)
-    // (left to itself only for Matern-5/2: at d = 2 recursion.hip's own split is 5-8 % faster on streams without gaps -- 8.8 against 9.6 us at
-    // 256 x 10^4 fp64 -- and 25 % slower on streams with them; at d = 3 the team kernel wins both, 10.0 against 12.1-12.9 us and 21-23 against 25-34)
-    if (gp->dxc64 && gp->opt_filter_plain_x != 0 && gp->opt_filter_team != 0 && (gp->d == 3 || gp->opt_filter_team == 1) && gp->opt_filter_split == 0 && variant == 0) {
-        const int rc = launch_filter_teamc_plain(gp->d, dtype, Ty, T, ld, gp->L, gp->dxc64, gp->dxc32, gp->dtp64, gp->dtp32, x_in, x, yhat, nll, (hipStream_t)stream, e0, e1,
-                                                 ld_out, nll ? nll_total : nullptr, gp->opt_filter_team);
-        if (rc != -1) return rc;
+    if (gp->gap_imp_version != gp->cb_version) {                 // the filters' impulse responses: once per parameter update
+        if (int rc = launch_gap_impulse(bank, c.kid, dtype, gp->L, c.cb64, c.cb32, io.stream)) return rc;
+        gp->gap_imp_version = gp->cb_version;
     }
-    // time split across the wavefronts of a workgroup when there are too few latents to fill the chip
+    SweepIo pass_io = io;                                        // (the total follows the last pass; the profile event pair rides on the first)
+    pass_io.total = nullptr;
+    StackOpts opts = c.opts;
+    opts.pass = StackPass::FirstAllGaps;
+    if (int rc = launch_filter_stream_x(c.kid, pass_io, c.cb64, c.cb32, opts)) return rc;
+    pass_io.ev0 = pass_io.ev1 = nullptr;
+    const GapArgs ga{bank.imp_out, bank.gpos, bank.gval, bank.gw, bank.gcap, bank.gstat};
+    const char* trace = getenv("MOIHGP_GAP_TRACE");               // diagnostics (the tests read it): synchronises the stream
+    const bool tracing = trace && trace[0] == '1';
+    if (tracing) MOIHGP_HIP_FATAL(hipMemsetAsync(bank.gstat, 0xFF, gp->L * sizeof(int), io.stream));
+    opts.pass = StackPass::Impute;
+    opts.gaps = &ga;
+    if (int rc = launch_filter_stream_x(c.kid, pass_io, c.cb64, c.cb32, opts)) return rc;
+    // what the recursion could not take (a filter with a memory longer than its table): the second pass, as without imputation
+    opts.pass = StackPass::SecondOnly;
+    opts.gaps = nullptr;
+    if (int rc = launch_filter_stream_x(c.kid, pass_io, c.cb64, c.cb32, opts)) return rc;
+    if (c.n_res) join_rescue(gp, io);
+    else if (io.nll && io.total) launch_nll_total(io.nll, gp->L, io.total, io.stream);
+    if (tracing) {
+        std::vector<int> st(gp->L);
+        MOIHGP_HIP_FATAL(hipMemcpyAsync(st.data(), bank.gstat, gp->L * sizeof(int), hipMemcpyDeviceToHost, io.stream));
+        MOIHGP_HIP_FATAL(hipStreamSynchronize(io.stream));
+        long taken = 0, solved = 0, gaps = 0, states = 0, why[6] = {0, 0, 0, 0, 0, 0};
+        for (int v : st) if (v >= 0) {
+            taken++;
+            if (v & 1) { solved++; gaps += (v & 0x3FFFFFFF) >> 1; states += (v >> 30) & 1; } else why[(v >> 1) < 6 ? (v >> 1) : 0]++;
+        }
+        fprintf(stderr, "moihgp gap imputation: %ld latents handed over, %ld solved, %ld gaps filled (%ld of the latents by the state form: memory beyond the table or "
+                "the ring; not solved: %ld response not finite or growing, %ld fill value not finite, %ld stream too long)\n", taken, solved, gaps, states, why[1], why[5], why[4]);
+    }
+    return 0;
+}
+
+// The stacked filter's kernels: a stacked model, or (plain_x) one of the reference's own through its one-component tables (launch_xc_from_cb).
+static int filter_stacked(moihgp_gp* gp, const SweepIo& io, bool plain_x) {
+    const size_t T = io.T;
+    StackedCall c;
+    c.kid = plain_x ? (gp->kernel | (1 << 4)) : gp->kernel;
+    c.cb64 = plain_x ? gp->dxc64 : gp->cb64;
+    c.cb32 = plain_x ? gp->dxc32 : gp->cb32;
+    const size_t slen = gp->L < 1024 ? gp->L * 16 : 0;              // per-slice NLL partials of the time split (few latents only)
+    if (slen && !gp->dxscratch) gp->dxscratch = dev_alloc<double>(slen);
+    if (gp->L >= 1024 && !gp->dlink) {                                               // hand-over records and flags of the second (broken-link) pass
+        gp->dlink = dev_alloc<double>(gp->L * 144);
+        gp->dlinkflags = dev_alloc<int>(gp->L);
+        MOIHGP_HIP_FATAL(hipMemsetAsync(gp->dlinkflags, 0, gp->L * sizeof(int), io.stream));
+    }
+    c.opts.slice_nll = gp->dxscratch; c.opts.slice_nll_len = slen;
+    c.opts.link_flags = gp->dlinkflags; c.opts.link_state = gp->dlink;       // (both NULL below 1024 latents)
+    c.opts.max_links = gp->opt_filter_maxlinks;
+    c.opts.team_mode = gp->opt_filter_team;
+    c.opts.tp64 = gp->dtp64; c.opts.tp32 = gp->dtp32;
+    c.n_res = (!plain_x && io.dtype == MOIHGP_F32 && gp->L >= 1024 && T > 0) ? (size_t)gp->n_unstable[2] : 0;
+    if (c.n_res)
+        if (int rc = rescue_side_sweep(gp, io, c)) return rc;
+    // Imputation, left to itself: at d >= 8 always (the second pass alone is 4-6 x slower there), below it -- where the second pass scans the chunks' own
+    // maps -- only for a bank without slow filters, whose latents would take both (measured, tools/filternan.py, 4096 x 10^4 at 1 % missing:
+    // 2 x Matern-5/2 0.81 -> 0.45 ms; 2 x Matern-3/2 at the bench's draw, 13 % of them slow, 0.37 -> 0.63)
+    const bool impute = !plain_x && gp->L >= 1024 && T > 0 && gp->opt_filter_split == 0 && (io.yhat || io.nll) &&
+                        (gp->opt_filter_impute == 1 || (gp->opt_filter_impute == -1 && (gp->d >= 8 || gp->n_unstable[3] == 0)));
+    // (its scratch is 12 or 20 bytes per tick and latent -- the lists of gaps, sized for the worst case: beyond 16 GB (MOIHGP_GAP_BANK_GB) the stream
+    // is too long for one call's worth of it and the second pass alone takes the gaps, as before round 4; slabs of a long stream stay below)
+    static const size_t gap_bank_limit = []() { const char* e = getenv("MOIHGP_GAP_BANK_GB"); const double gb = e ? atof(e) : 16.0; return (size_t)(gb * 1073741824.0); }();
+    if (impute && gap_bank_bytes(gp->d, io.dtype, gp->L, T) <= gap_bank_limit) return imputation_sweeps(gp, io, c);
+    return stacked_sweep(gp, io, c);
+}
+
+// Few latents, streams of 2 .. 8 segments of the reference's own models: one workgroup per latent, eight wavefronts (the stacked filter's team
+// kernel, recursion_x.hip).  Returns -1 if the kernel does not take the call.
+// (left to itself only for Matern-5/2: at d = 2 recursion.hip's own split is 5-8 % faster on streams without gaps -- 8.8 against 9.6 us at
+// 256 x 10^4 fp64 -- and 25 % slower on streams with them; at d = 3 the team kernel wins both, 10.0 against 12.1-12.9 us and 21-23 against 25-34)
+static int team_kernel_attempt(moihgp_gp* gp, const SweepIo& io, int variant) {
+    if (!(gp->dxc64 && gp->opt_filter_plain_x != 0 && gp->opt_filter_team != 0 && (gp->d == 3 || gp->opt_filter_team == 1) && gp->opt_filter_split == 0 && variant == 0)) return -1;
+    return launch_filter_teamc_plain(gp->d, io, gp->dxc64, gp->dxc32, gp->dtp64, gp->dtp32, gp->opt_filter_team);
+}
+
+// recursion.hip's sweep: time split across the wavefronts of a workgroup when there are too few latents to fill the chip
+static int filter_time_split(moihgp_gp* gp, const SweepIo& io, int variant) {
+    const size_t T = io.T;
     int nsplit = 1, nbig = 1; size_t Tslice = T;
-    filter_split_plan(dtype, T, gp->L, &nsplit, &Tslice, &nbig);
+    filter_split_plan(io.dtype, T, gp->L, &nsplit, &Tslice, &nbig);
     if (gp->opt_filter_split != 0) {                                    // test / tuning hook: force the slice count (1 = off)
         int n = gp->opt_filter_split;
-        const size_t seg = 64 * (size_t)(dtype == 0 ? kChunk64 : kChunk32);
+        const size_t seg = 64 * (size_t)(io.dtype == 0 ? kChunk64 : kChunk32);
         if (n <= 1 || T == 0) { nsplit = 1; Tslice = T; nbig = 1; }
         else {
             if (n > 8) n = 8;
@@ -945,29 +979,44 @@ static int filter_stream_io_impl(moihgp_gp* gp, int dtype, const void* Ty, size_
             Tslice = per * seg; nsplit = (int)((T + Tslice - 1) / Tslice); nbig = nsplit;      // forced count: equal slices
         }
     }
-    return launch_filter_stream(gp->d, dtype, Ty, T, ld, gp->L, gp->cb64, gp->cb32, x_in, x, yhat, nll, (hipStream_t)stream, variant, e0, e1,
-                                nsplit, Tslice, gp->n_unstable[dtype == MOIHGP_F64 ? 0 : 1], nll_total, nbig, ld_out);
+    return launch_filter_stream(gp->d, io, gp->cb64, gp->cb32, variant, nsplit, Tslice, gp->n_unstable[io.dtype == MOIHGP_F64 ? 0 : 1], nbig);
+}
+
+static int filter_stream_io_impl(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld, const void* x_in, void* x, void* yhat, double* nll,
+                            double* nll_total, void* stream, size_t ld_out = 0) {
+    if (int rc = check_sweep_call(gp, dtype, Ty, T, ld, x_in, x)) return rc;
+    note_user_stream(gp, (hipStream_t)stream);
+    if (int rc = check_nll_total(nll_total, nll)) return rc;
+    if (nll_total && T == 0) MOIHGP_HIP_FATAL(hipMemsetAsync(nll_total, 0, sizeof(double), (hipStream_t)stream));
+    SweepIo io = sweep_io(dtype, Ty, T, ld, gp->L, x_in, x, yhat, ld_out, nll, nll_total, (hipStream_t)stream);
+    const size_t epv = dtype == MOIHGP_F64 ? 2 : 4;
+    if (yhat && ((uintptr_t)yhat & 15) != 0) { set_last_error("yhat base must be 16-byte aligned"); return 1; }
+    if (yhat && (io.ld_out % epv != 0 || io.ld_out < (T + epv - 1) / epv * epv)) {
+        set_last_error("ld_out (%zu) must be a multiple of %zu and >= T rounded up to it", io.ld_out, epv);
+        return 1;
+    }
+    const int variant = gp->opt_filter_variant;              // tuning probes: only a -DMOIHGP_TUNING build accepts a non-zero value
+    claim_profile_events(gp, io);
+    // the reference's own models through the stacked filter's kernels: only when asked for (option filter_plain_x = 1)
+    const bool plain_x = !kernel_stack(gp->kernel) && gp->dxc64 && variant == 0 && gp->opt_filter_split == 0 && gp->opt_filter_plain_x == 1;
+    if (kernel_stack(gp->kernel) || plain_x) return filter_stacked(gp, io, plain_x);
+    if (const int rc = team_kernel_attempt(gp, io, variant); rc != -1) return rc;
+    return filter_time_split(gp, io, variant);
 }
 
 // segment-major streams (include/moihgp.h: moihgp_filter_stream_tiled)
 static int filter_stream_tiled_impl(moihgp_gp* gp, int dtype, const void* Ty, size_t T, const void* x_in, void* x, void* yhat, double* nll, double* nll_total,
                                     void* stream) {
-    if (!gp) { set_last_error("null handle"); return 1; }
-    if (dtype != MOIHGP_F64 && dtype != MOIHGP_F32) { set_last_error("dtype must be MOIHGP_F64 or MOIHGP_F32"); return 1; }
+    if (int rc = check_handle_dtype(gp, dtype)) return rc;
     if (!x || !x_in || (T > 0 && !Ty)) { set_last_error("null stream/state pointer"); return 1; }
     if (((uintptr_t)Ty & 15) != 0 || (yhat && ((uintptr_t)yhat & 15) != 0)) { set_last_error("stream base must be 16-byte aligned"); return 1; }
     if (kernel_stack(gp->kernel)) { set_last_error("segment-major streams: the reference's own models only (d = 2, 3); stacked models take series-major streams"); return 3; }
-    if (nll_total && !nll) { set_last_error("nll_total needs the per-latent nll buffer"); return 1; }
+    if (int rc = check_nll_total(nll_total, nll)) return rc;
     note_user_stream(gp, (hipStream_t)stream);
     if (nll_total && T == 0) MOIHGP_HIP_FATAL(hipMemsetAsync(nll_total, 0, sizeof(double), (hipStream_t)stream));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (!gp->prof_ev.empty() && 2 * (size_t)(gp->prof_n + 1) <= gp->prof_ev.size() && (gp->prof_seen++ % gp->prof_stride) == 0) {
-        e0 = gp->prof_ev[2 * gp->prof_n];
-        e1 = gp->prof_ev[2 * gp->prof_n + 1];
-        gp->prof_n++;
-    }
-    return launch_filter_stream_tiled(gp->d, dtype, Ty, T, gp->L, gp->cb64, gp->cb32, x_in, x, yhat, nll, (hipStream_t)stream, e0, e1,
-                                      gp->n_unstable[dtype == MOIHGP_F64 ? 0 : 1], nll_total, gp->opt_filter_variant);
+    SweepIo io = sweep_io(dtype, Ty, T, 0, gp->L, x_in, x, yhat, 0, nll, nll_total, (hipStream_t)stream);     // (segment-major: no row strides)
+    claim_profile_events(gp, io);
+    return launch_filter_stream_tiled(gp->d, io, gp->cb64, gp->cb32, gp->n_unstable[dtype == MOIHGP_F64 ? 0 : 1], gp->opt_filter_variant);
 }
 
 int moihgp_filter_stream_tiled(moihgp_gp* gp, int dtype, const void* Ty, size_t T, const void* x_in, void* x, void* yhat, double* nll, double* nll_total,

@@ -135,21 +135,56 @@ void launch_rescue_scatter(const int* idx, size_t n, const double* rows, size_t 
                            float* yhat, size_t ldo, float* x, double* nll, hipStream_t s);
 // stationary_x.hip: the reference's own models (d = 2, 3) in the stacked layout, for the few-latents team kernel: [n][xc_size(d)] from the CB blocks
 void launch_xc_from_cb(int d, const double* cb64, size_t n, double* xc64, float* xc32, hipStream_t stream);
-// stack_dispatch.hip: the team kernel for those models, if the stream and the bank suit it (returns -1 if not: the caller carries on)
-int launch_filter_teamc_plain(int d, int dtype, const void* Ty, size_t T, size_t ld, size_t L, const double* xc64, const float* xc32, const double* tp64, const float* tp32,
-                              const void* xin, void* x, void* yhat, double* nll, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, size_t ldo, double* total, int team_mode);
+// ---- filter sweeps: what every launcher of one is handed ----
+// The stream of one call, where its results go, and the queue it runs on.  Filled once per call (capi.cpp); the launchers unpack it at the
+// kernel launch line -- a kernel never sees the record.
+struct SweepIo {
+    int dtype;                          // 0 = fp64, 1 = fp32 (MOIHGP_F64 / MOIHGP_F32): the scalar type behind the void pointers
+    const void* Ty; size_t T, ld, L;    // [L][ld] series-major, T ticks per row (segment-major streams: ld unused, 0)
+    const void* xin; void* x;           // [L][d] start state / end state (may alias)
+    void* yhat = nullptr;               // [L][ld_out] filtered means, or NULL
+    size_t ld_out = 0;                  // row stride of yhat: always set where yhat is (sweep_io() fills in ld when the caller leaves it 0)
+    double* nll = nullptr;              // [L] or NULL
+    double* total = nullptr;            // device scalar: sum of nll[], or NULL
+    hipStream_t stream = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;   // profile event pair around the sweep kernel, or NULL
+};
+inline SweepIo sweep_io(int dtype, const void* Ty, size_t T, size_t ld, size_t L, const void* xin, void* x, void* yhat, size_t ld_out, double* nll,
+                        double* total, hipStream_t stream, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr) {
+    return SweepIo{dtype, Ty, T, ld, L, xin, x, yhat, ld_out ? ld_out : ld, nll, total, stream, ev0, ev1};
+}
+// Which of its passes the stacked sweep runs (many latents, L >= 1024, unless noted).
+enum class StackPass {
+    Auto,             // first pass, then the second (broken-link) pass over the latents the first stopped at a gap; few latents: team kernel or time split
+    TeamOnly,         // the reference's own models: the few-latents team kernel or nothing (returns -1: the caller carries on with recursion.hip)
+    FirstAllGaps,     // the first pass alone, handing over EVERY latent that holds a gap
+    SecondOnly,       // the second pass alone
+    FirstPredicted,   // the first pass alone, writing predicted observations HA x instead of filtered means, no NLL (the filters' impulse responses)
+    Impute,           // the imputation sweep of the latents the first pass flagged (filter_x_gaps_a / _b_kernel): needs `gaps`
+};
+struct GapArgs;
+// What only the stacked path needs.
+struct StackOpts {
+    StackPass pass = StackPass::Auto;
+    int slices = 0;                     // tuning / test hook (few latents): 0 = automatic, 1 = no time split, n > 1 = n slices
+    double* slice_nll = nullptr;        // [slice_nll_len] per-slice NLL partials of the time split
+    size_t slice_nll_len = 0;
+    // with both (L >= 1024): segments with few gaps are handled as broken links by a second pass instead of being walked tick by tick
+    int* link_flags = nullptr;          // [L]
+    double* link_state = nullptr;       // [L][144]
+    int max_links = -1;                 // -1: automatic
+    int team_mode = -1;                 // few latents: -1 automatic, 0 never, 1 always use a team kernel, 2 the 32-tick one
+    const double* tp64 = nullptr;       // launch_team_powers' tables, or NULL: no chunk-templated team kernel
+    const float* tp32 = nullptr;
+    const GapArgs* gaps = nullptr;      // StackPass::Impute only (host memory)
+};
+// stack_dispatch.hip: the team kernel for the reference's own models, if the stream and the bank suit it (returns -1 if not: the caller carries on)
+int launch_filter_teamc_plain(int d, const SweepIo& io, const double* xc64, const float* xc32, const double* tp64, const float* tp32, int team_mode);
 // recursion_x.hip: scan powers of the chunk-templated team kernel (few latents), [L][5][team_powers_elems(d)] in both precisions; after every launch_stack_update
 constexpr size_t team_powers_elems(int d) { return 5 * (size_t)(7 * ((d * d + 15) / 16 * 16) + 16); }
 void launch_team_powers(int kernel, const double* cb64, size_t L, double* tp64, float* tp32, hipStream_t stream);
-int launch_filter_stream_x(int kernel, int dtype, const void* Ty, size_t T, size_t ld, size_t L, const double* cb64, const float* cb32,
-                           const void* xin, void* x, void* yhat, double* nll, hipStream_t stream, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr,
-                           double* scratch = nullptr /* [scratch_len] per-slice NLL partials of the time split */, size_t scratch_len = 0,
-                           int force_slices = 0 /* tuning / test hook: 1 = no split, n > 1 = n slices */, size_t ld_out = 0 /* row stride of yhat; 0 = ld */,
-                           int* link_flags = nullptr /* [L] */, double* link_state = nullptr /* [L][144] */, double* total = nullptr /* sum of nll[] */,
-                           int max_links = -1 /* -1: automatic */, int team_mode = -1 /* few latents: -1 automatic, 0 never, 1 always use a team kernel, 2 the 32-tick one */,
-                           const double* tp64 = nullptr, const float* tp32 = nullptr /* launch_team_powers' tables, or NULL: no chunk-templated team kernel */
-                           /* scratch; with both (L >= 1024): segments with few gaps are handled as broken links by a second pass instead of
-                              being walked tick by tick */);
+// stack_dispatch.hip -> recursion_x.hip: the filter sweep of a stacked model; cb64 / cb32: its XC blocks
+int launch_filter_stream_x(int kernel, const SweepIo& io, const double* cb64, const float* cb32, const StackOpts& opts);
 
 // grad_gen.hip: gradient sweep of the latents flagged 1 in fallback[] (missing ticks), scan over the chunks' affine maps; clears the flag
 int launch_grad_gen(int d, int dtype, const void* Ty, size_t T, size_t ld, size_t L, const double* cb64, const float* cb32, void* x, void* dx,
@@ -172,7 +207,7 @@ int launch_grad_scan_x(int kernel, int dtype, const void* Ty, size_t Tpar, size_
 // a latent that holds gaps around a scalar recursion over its gaps).  gaps_x.hip: the scratch it works in and the filters' impulse
 // responses it needs.
 constexpr int kGapSMax = 1024;        // impulse-response table per latent (ticks); beyond it the response must be negligible
-struct GapArgs {                      // what launch_filter_stream_x(force_slices = -7) finds behind its `scratch` argument (host memory)
+struct GapArgs {                      // StackOpts::gaps: the scratch of StackPass::Impute
     const void* imp;                  // [L][kGapSMax] impulse responses, the stream's scalar type
     int* gpos; void* gval; void* gw;  // [L][gcap] the gaps' ticks / their predictions / their fill values
     size_t gcap;
@@ -191,8 +226,7 @@ GapBank gap_bank_carve(void* base, int d, int dtype, size_t L, size_t T);
 int gap_bank_init(const GapBank& b, int d, int dtype, size_t L, hipStream_t s);
 int launch_gap_impulse(const GapBank& b, int kernel, int dtype, size_t L, const double* cb64, const float* cb32, hipStream_t s);
 // recursion.hip: the same sweep over segment-major streams [ceil(T / SEG)][L][SEG], SEG = 4096 / sizeof(scalar) ticks (d = 2, 3)
-int launch_filter_stream_tiled(int d, int dtype, const void* Ty, size_t T, size_t L, const double* cb64, const float* cb32, const void* xin, void* x,
-                               void* yhat, double* nll, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, int n_unstable, double* total, int variant = 0);
+int launch_filter_stream_tiled(int d, const SweepIo& io, const double* cb64, const float* cb32, int n_unstable, int variant = 0);
 // smoother.hip: steady-state RTS smoothing (include/moihgp.h moihgp_smooth_stream).  Per-latent fp64 block SM<D> of sm_size(d) doubles
 // (stream_tables.h, which names its fields).
 void launch_smoother_tables(int kernel, int d, const double* cb64, size_t L, double* tabs, hipStream_t stream);
@@ -221,13 +255,9 @@ void launch_sample_noise(unsigned long long seed, unsigned latent0, size_t L, un
 // series-major [L][ld] <-> segment-major [ceil(T / SEG)][L][SEG] (to_tiled != 0: src is series-major; ticks past T are written as zeros)
 int launch_stream_retile(int dtype, const void* src, void* dst, size_t L, size_t T, size_t ld, int to_tiled, hipStream_t stream);
 // recursion.hip: batched sweeps over series-major streams.
-int launch_filter_stream(int d, int dtype, const void* Ty, size_t T, size_t ld, size_t L,
-                         const double* cb64, const float* cb32, const void* xin /* start state */, void* x /* end state, may alias xin */,
-                         void* yhat, double* nll,
-                         hipStream_t stream, int variant = 0, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr,
+int launch_filter_stream(int d, const SweepIo& io, const double* cb64, const float* cb32, int variant = 0,
                          int nsplit = 1, size_t Tslice = 0, int n_unstable = 0 /* latents with SCANOK == 0 in this dtype's blocks */,
-                         double* total = nullptr /* device scalar: sum of nll[] (optional) */, int nbig = 0 /* see filter_split_plan; 0 = all slices alike */,
-                         size_t ld_out = 0 /* row stride of yhat; 0 = ld */);
+                         int nbig = 0 /* see filter_split_plan; 0 = all slices alike */);
 void launch_nll_total(const double* nll, size_t L, double* total, hipStream_t stream);
 // Time split for small L (slices of one latent = wavefronts of one workgroup): nsplit == 1 means none.
 void filter_split_plan(int dtype, size_t T, size_t L, int* nsplit, size_t* Tslice, int* nbig /* leading slices of Tslice ticks; the rest hold one segment less */);

@@ -87,8 +87,10 @@ int gap_bank_init(const GapBank& b, int d, int dtype, size_t L, hipStream_t s) {
 
 // The impulse responses of all L filters into b.imp_out: b.imp_out[l][k + 1] = s_k of latent l.  Asynchronous on `s`.
 int launch_gap_impulse(const GapBank& b, int kernel, int dtype, size_t L, const double* cb64, const float* cb32, hipStream_t s) {
-    return launch_filter_stream_x(kernel, dtype, b.imp_in, kGapSMax, kGapSMax, L, cb64, cb32, b.xz, b.x1, b.imp_out, nullptr, s, nullptr, nullptr, nullptr, 0,
-                                  -6, kGapSMax, nullptr, nullptr, nullptr, -1, 0, nullptr, nullptr);
+    StackOpts opts;
+    opts.pass = StackPass::FirstPredicted;
+    opts.team_mode = 0;
+    return launch_filter_stream_x(kernel, sweep_io(dtype, b.imp_in, kGapSMax, kGapSMax, L, b.xz, b.x1, b.imp_out, kGapSMax, nullptr, nullptr, s), cb64, cb32, opts);
 }
 
 }  // namespace moihgp

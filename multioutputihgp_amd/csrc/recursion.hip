@@ -1306,15 +1306,17 @@ filter_dma_kernel(const T* __restrict__ Ty, size_t Tlen, size_t ld, size_t L, co
 }
 
 template <typename T, int D, int CK, int NP, int MINW, bool TILED = false>
-int launch_filter_dma_t(const void* Ty, size_t Tlen, size_t ld, size_t L, const T* cbT, const double* cb64, const void* xin, void* x,
-                        void* yhat, double* nll, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, int n_unstable, double* total, size_t ldo) {
+int launch_filter_dma_t(const SweepIo& io, const T* cbT, const double* cb64, int n_unstable) {
+    const size_t Tlen = io.T, ld = io.ld, L = io.L, ldo = io.ld_out;
+    double* const nll = io.nll;
+    const hipStream_t stream = io.stream;
     constexpr int SPL = ((D * D * (int)sizeof(T)) + 15) / 16 * 16;
     constexpr size_t smem = (size_t)kWavesPerBlock * (NP * 1024 + 4 * SPL);
     dim3 block(64 * kWavesPerBlock), grid((unsigned)((L + kWavesPerBlock - 1) / kWavesPerBlock));
-    const T* ty = static_cast<const T*>(Ty);
-    const T* xi = static_cast<const T*>(xin);
-    T* xs = static_cast<T*>(x);
-    T* yh = static_cast<T*>(yhat);
+    const T* ty = static_cast<const T*>(io.Ty);
+    const T* xi = static_cast<const T*>(io.xin);
+    T* xs = static_cast<T*>(io.x);
+    T* yh = static_cast<T*>(io.yhat);
 #define MOIHGP_DMA_LAUNCH(W_, N_)                                                                                                     \
     do {                                                                                                                              \
         auto kfn = filter_dma_kernel<T, D, CK, W_, N_, NP, MINW, TILED>;                                                              \
@@ -1322,25 +1324,26 @@ int launch_filter_dma_t(const void* Ty, size_t Tlen, size_t ld, size_t L, const 
             static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem); \
             if (attr != hipSuccess) { set_last_error("filter_dma_kernel: %zu bytes of LDS refused: %s", smem, hipGetErrorString(attr)); return 2; } \
         }                                                                                                                             \
-        hipExtLaunchKernelGGL(kfn, grid, block, smem, stream, ev0, ev1, 0, ty, Tlen, ld, L, cbT, cb64, xi, xs, yh, nll, ldo);         \
+        hipExtLaunchKernelGGL(kfn, grid, block, smem, stream, io.ev0, io.ev1, 0, ty, Tlen, ld, L, cbT, cb64, xi, xs, yh, nll, ldo);         \
     } while (0)
-    if (yhat && nll) MOIHGP_DMA_LAUNCH(true, true);
-    else if (yhat) MOIHGP_DMA_LAUNCH(true, false);
+    if (yh && nll) MOIHGP_DMA_LAUNCH(true, true);
+    else if (yh) MOIHGP_DMA_LAUNCH(true, false);
     else if (nll) MOIHGP_DMA_LAUNCH(false, true);
     else MOIHGP_DMA_LAUNCH(false, false);
 #undef MOIHGP_DMA_LAUNCH
     if (n_unstable > 0)
         hipLaunchKernelGGL((filter_seq_kernel<T, D, TILED>), dim3((unsigned)((L + 63) / 64)), dim3(64), 0, stream, ty, Tlen, ld, L, cbT, cb64, xi, xs, yh, nll, ldo);
-    if (total && nll) hipLaunchKernelGGL(nll_total_kernel, dim3(1), dim3(1024), 0, stream, nll, L, total);
+    if (io.total && nll) hipLaunchKernelGGL(nll_total_kernel, dim3(1), dim3(1024), 0, stream, nll, L, io.total);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_last_error("filter_dma_kernel launch: %s", hipGetErrorString(e)); return 2; }
     return 0;
 }
 
 template <typename T, int D, int CK, int MINW, bool SPLIT>
-int launch_filter_t(const void* Ty, size_t Tlen, size_t ld, size_t L, const T* cbT, const double* cb64, const void* xin, void* x,
-                    void* yhat, double* nll, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, int nsplit, size_t Tslice, int n_unstable,
-                    double* total, int nbig, size_t ldo, int team_ok = 1) {
+int launch_filter_t(const SweepIo& io, const T* cbT, const double* cb64, int nsplit, size_t Tslice, int n_unstable, int nbig, int team_ok = 1) {
+    const size_t Tlen = io.T, ld = io.ld, L = io.L, ldo = io.ld_out;
+    double* const nll = io.nll;
+    const hipStream_t stream = io.stream;
     dim3 block(SPLIT ? 64 * nsplit : 64 * kWavesPerBlock);
     dim3 grid(SPLIT ? (unsigned)L : (unsigned)((L + kWavesPerBlock - 1) / kWavesPerBlock));
     constexpr size_t tile = 64 * (CK / (16 / sizeof(T)) + 1) * 16;                    // padded LDS tile per wave
@@ -1349,22 +1352,22 @@ int launch_filter_t(const void* Ty, size_t Tlen, size_t ld, size_t L, const T* c
                         (SPLIT ? (size_t)kTeamMaxSegs * D * sizeof(double) + 32 : 0);             // (team path: zero-start end states of the segments, flag)
     // team path of the split: every slice fits kTeamSeg segments kept in registers
     const int team = (SPLIT && team_ok && Tslice <= (size_t)kTeamSeg * 64 * CK && (Tlen + 64 * CK - 1) / (64 * CK) <= (size_t)kTeamMaxSegs) ? 1 : 0;
-    const T* ty = static_cast<const T*>(Ty);
-    const T* xi = static_cast<const T*>(xin);
-    T* xs = static_cast<T*>(x);
-    T* yh = static_cast<T*>(yhat);
+    const T* ty = static_cast<const T*>(io.Ty);
+    const T* xi = static_cast<const T*>(io.xin);
+    T* xs = static_cast<T*>(io.x);
+    T* yh = static_cast<T*>(io.yhat);
     // hipExtLaunchKernelGGL attaches the (optional) events to the dispatch itself: kernel-exact timing
-    if (yhat && nll)
-        hipExtLaunchKernelGGL((filter_scan_kernel<T, D, CK, true, true, MINW, SPLIT>), grid, block, smem, stream, ev0, ev1, 0, ty, Tlen, ld, L, cbT, cb64, xi, xs, yh, nll, nsplit, Tslice, nbig, ldo, team);
-    else if (yhat)
-        hipExtLaunchKernelGGL((filter_scan_kernel<T, D, CK, true, false, MINW, SPLIT>), grid, block, smem, stream, ev0, ev1, 0, ty, Tlen, ld, L, cbT, cb64, xi, xs, yh, nll, nsplit, Tslice, nbig, ldo, team);
+    if (yh && nll)
+        hipExtLaunchKernelGGL((filter_scan_kernel<T, D, CK, true, true, MINW, SPLIT>), grid, block, smem, stream, io.ev0, io.ev1, 0, ty, Tlen, ld, L, cbT, cb64, xi, xs, yh, nll, nsplit, Tslice, nbig, ldo, team);
+    else if (yh)
+        hipExtLaunchKernelGGL((filter_scan_kernel<T, D, CK, true, false, MINW, SPLIT>), grid, block, smem, stream, io.ev0, io.ev1, 0, ty, Tlen, ld, L, cbT, cb64, xi, xs, yh, nll, nsplit, Tslice, nbig, ldo, team);
     else if (nll)
-        hipExtLaunchKernelGGL((filter_scan_kernel<T, D, CK, false, true, MINW, SPLIT>), grid, block, smem, stream, ev0, ev1, 0, ty, Tlen, ld, L, cbT, cb64, xi, xs, yh, nll, nsplit, Tslice, nbig, ldo, team);
+        hipExtLaunchKernelGGL((filter_scan_kernel<T, D, CK, false, true, MINW, SPLIT>), grid, block, smem, stream, io.ev0, io.ev1, 0, ty, Tlen, ld, L, cbT, cb64, xi, xs, yh, nll, nsplit, Tslice, nbig, ldo, team);
     else
-        hipExtLaunchKernelGGL((filter_scan_kernel<T, D, CK, false, false, MINW, SPLIT>), grid, block, smem, stream, ev0, ev1, 0, ty, Tlen, ld, L, cbT, cb64, xi, xs, yh, nll, nsplit, Tslice, nbig, ldo, team);
+        hipExtLaunchKernelGGL((filter_scan_kernel<T, D, CK, false, false, MINW, SPLIT>), grid, block, smem, stream, io.ev0, io.ev1, 0, ty, Tlen, ld, L, cbT, cb64, xi, xs, yh, nll, nsplit, Tslice, nbig, ldo, team);
     if (n_unstable > 0)
         hipLaunchKernelGGL((filter_seq_kernel<T, D>), dim3((unsigned)((L + 63) / 64)), dim3(64), 0, stream, ty, Tlen, ld, L, cbT, cb64, xi, xs, yh, nll, ldo);
-    if (total && nll) hipLaunchKernelGGL(nll_total_kernel, dim3(1), dim3(1024), 0, stream, nll, L, total);
+    if (io.total && nll) hipLaunchKernelGGL(nll_total_kernel, dim3(1), dim3(1024), 0, stream, nll, L, io.total);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_last_error("filter_scan_kernel launch: %s", hipGetErrorString(e)); return 2; }
     return 0;
@@ -1427,14 +1430,14 @@ int launch_stream_retile(int dtype, const void* src, void* dst, size_t L, size_t
 
 // The sweep over SEGMENT-MAJOR streams ([ceil(T / SEG)][L][SEG], SEG = 4096 / sizeof(scalar) ticks; filter_dma_kernel TILED): the reference's
 // own models (d = 2, 3), any number of latents (one wavefront per latent: meant for the many-latent shapes).
-int launch_filter_stream_tiled(int d, int dtype, const void* Ty, size_t T, size_t L, const double* cb64, const float* cb32, const void* xin, void* x,
-                               void* yhat, double* nll, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, int n_unstable, double* total, int variant) {
-    if (L == 0) return 0;
+int launch_filter_stream_tiled(int d, const SweepIo& io, const double* cb64, const float* cb32, int n_unstable, int variant) {
+    if (io.L == 0) return 0;
+    const int dtype = io.dtype;
 #ifdef MOIHGP_TUNING
     if (variant >= 20 && variant < 30 && d == 3) {        // ring length / waves per SIMD probes, as for the series-major sweep
 #define MOIHGP_DMA_PROBE_T(V_, NP_, MW_)                                                                                                \
-        if (variant == V_) return dtype == 0 ? launch_filter_dma_t<double, 3, kChunk64, NP_, MW_, true>(Ty, T, 0, L, cb64, cb64, xin, x, yhat, nll, stream, ev0, ev1, n_unstable, total, 0) \
-                                             : launch_filter_dma_t<float, 3, kChunk32, NP_, MW_, true>(Ty, T, 0, L, cb32, cb64, xin, x, yhat, nll, stream, ev0, ev1, n_unstable, total, 0)
+        if (variant == V_) return dtype == 0 ? launch_filter_dma_t<double, 3, kChunk64, NP_, MW_, true>(io, cb64, cb64, n_unstable) \
+                                             : launch_filter_dma_t<float, 3, kChunk32, NP_, MW_, true>(io, cb32, cb64, n_unstable)
         MOIHGP_DMA_PROBE_T(21, 9, 4); MOIHGP_DMA_PROBE_T(22, 12, 3); MOIHGP_DMA_PROBE_T(23, 16, 2); MOIHGP_DMA_PROBE_T(24, 8, 3); MOIHGP_DMA_PROBE_T(25, 12, 2);
 #undef MOIHGP_DMA_PROBE_T
     }
@@ -1442,24 +1445,22 @@ int launch_filter_stream_tiled(int d, int dtype, const void* Ty, size_t T, size_
     (void)variant;
 #endif
     if (dtype == 0) {
-        if (d == 2) return launch_filter_dma_t<double, 2, kChunk64, kDmaRing64, kDmaWaves64, true>(Ty, T, 0, L, cb64, cb64, xin, x, yhat, nll, stream, ev0, ev1, n_unstable, total, 0);
-        return launch_filter_dma_t<double, 3, kChunk64, kDmaRing64, kDmaWaves64, true>(Ty, T, 0, L, cb64, cb64, xin, x, yhat, nll, stream, ev0, ev1, n_unstable, total, 0);
+        if (d == 2) return launch_filter_dma_t<double, 2, kChunk64, kDmaRing64, kDmaWaves64, true>(io, cb64, cb64, n_unstable);
+        return launch_filter_dma_t<double, 3, kChunk64, kDmaRing64, kDmaWaves64, true>(io, cb64, cb64, n_unstable);
     }
-    if (d == 2) return launch_filter_dma_t<float, 2, kChunk32, kDmaRing32, kDmaWaves32, true>(Ty, T, 0, L, cb32, cb64, xin, x, yhat, nll, stream, ev0, ev1, n_unstable, total, 0);
-    return launch_filter_dma_t<float, 3, kChunk32, kDmaRing32, kDmaWaves32, true>(Ty, T, 0, L, cb32, cb64, xin, x, yhat, nll, stream, ev0, ev1, n_unstable, total, 0);
+    if (d == 2) return launch_filter_dma_t<float, 2, kChunk32, kDmaRing32, kDmaWaves32, true>(io, cb32, cb64, n_unstable);
+    return launch_filter_dma_t<float, 3, kChunk32, kDmaRing32, kDmaWaves32, true>(io, cb32, cb64, n_unstable);
 }
 
-int launch_filter_stream(int d, int dtype, const void* Ty, size_t T, size_t ld, size_t L, const double* cb64,
-                         const float* cb32, const void* xin, void* x, void* yhat, double* nll, hipStream_t stream, int variant,
-                         hipEvent_t ev0, hipEvent_t ev1, int nsplit, size_t Tslice, int n_unstable, double* total, int nbig, size_t ldo) {
-    if (L == 0) return 0;
-    if (ldo == 0) ldo = ld;
+int launch_filter_stream(int d, const SweepIo& io, const double* cb64, const float* cb32, int variant, int nsplit, size_t Tslice, int n_unstable, int nbig) {
+    if (io.L == 0) return 0;
+    const int dtype = io.dtype;
     if (nsplit > kMaxSplit) { set_last_error("nsplit > %d", kMaxSplit); return 1; }
     if (nbig <= 0 || nbig > nsplit) nbig = nsplit;
 #define MOIHGP_FILTER_CASE(TT, DD, CKK, MW, CB)                                                                                   \
     do {                                                                                                                          \
-        if (nsplit > 1) return launch_filter_t<TT, DD, CKK, 1, true>(Ty, T, ld, L, CB, cb64, xin, x, yhat, nll, stream, ev0, ev1, nsplit, Tslice, n_unstable, total, nbig, ldo); \
-        return launch_filter_t<TT, DD, CKK, MW, false>(Ty, T, ld, L, CB, cb64, xin, x, yhat, nll, stream, ev0, ev1, 1, T, n_unstable, total, 1, ldo);        \
+        if (nsplit > 1) return launch_filter_t<TT, DD, CKK, 1, true>(io, CB, cb64, nsplit, Tslice, n_unstable, nbig); \
+        return launch_filter_t<TT, DD, CKK, MW, false>(io, CB, cb64, 1, io.T, n_unstable, 1);                            \
     } while (0)
     // register caps: fp32 <= 128 VGPRs (4 waves/SIMD: all 4096 wavefronts of a 4096-latent shard resident),
     // fp64 uncapped (188 VGPRs, 2 waves/SIMD: capping it to 168 spills and is 35 % slower)
@@ -1468,10 +1469,10 @@ int launch_filter_stream(int d, int dtype, const void* Ty, size_t T, size_t ld, 
     // loads (4), both (6), and the staging-only kernel (9), which does NO arithmetic.  None of them is part of the shipped library.
     if (variant == 1 && dtype == 0 && d == 3) MOIHGP_FILTER_CASE(double, 3, kChunk64, 3, cb64);
     if (dtype == 1 && d == 3 && (variant == 2 || variant == 4 || variant == 6 || variant == 9)) {
-        dim3 block(64 * kWavesPerBlock), grid((unsigned)((L + kWavesPerBlock - 1) / kWavesPerBlock));
+        dim3 block(64 * kWavesPerBlock), grid((unsigned)((io.L + kWavesPerBlock - 1) / kWavesPerBlock));
         const size_t sm = (size_t)kWavesPerBlock * (64 * 5 * 16 + 36 * 4);
-#define MOIHGP_PROBE(MW, DBG_) hipExtLaunchKernelGGL((filter_scan_kernel<float, 3, kChunk32, true, true, MW, false, DBG_>), grid, block, sm, stream, ev0, ev1, 0, \
-                                                     (const float*)Ty, T, ld, L, cb32, cb64, (const float*)xin, (float*)x, (float*)yhat, nll, 1, T, 1, ldo, 0)
+#define MOIHGP_PROBE(MW, DBG_) hipExtLaunchKernelGGL((filter_scan_kernel<float, 3, kChunk32, true, true, MW, false, DBG_>), grid, block, sm, io.stream, io.ev0, io.ev1, 0, \
+                                                     (const float*)io.Ty, io.T, io.ld, io.L, cb32, cb64, (const float*)io.xin, (float*)io.x, (float*)io.yhat, io.nll, 1, io.T, 1, io.ld_out, 0)
         if (variant == 2) MOIHGP_PROBE(4, 2);
         else if (variant == 4) MOIHGP_PROBE(4, 4);
         else if (variant == 6) MOIHGP_PROBE(4, 6);
@@ -1483,8 +1484,8 @@ int launch_filter_stream(int d, int dtype, const void* Ty, size_t T, size_t ld, 
     // LDS-DMA kernel, ring length / waves per SIMD probes (d = 3): 20 + k
     if (variant >= 20 && variant < 30 && d == 3 && nsplit == 1) {
 #define MOIHGP_DMA_PROBE(V_, NP_, MW_)                                                                                                  \
-        if (variant == V_) return dtype == 0 ? launch_filter_dma_t<double, 3, kChunk64, NP_, MW_>(Ty, T, ld, L, cb64, cb64, xin, x, yhat, nll, stream, ev0, ev1, n_unstable, total, ldo) \
-                                             : launch_filter_dma_t<float, 3, kChunk32, NP_, MW_>(Ty, T, ld, L, cb32, cb64, xin, x, yhat, nll, stream, ev0, ev1, n_unstable, total, ldo)
+        if (variant == V_) return dtype == 0 ? launch_filter_dma_t<double, 3, kChunk64, NP_, MW_>(io, cb64, cb64, n_unstable) \
+                                             : launch_filter_dma_t<float, 3, kChunk32, NP_, MW_>(io, cb32, cb64, n_unstable)
         MOIHGP_DMA_PROBE(20, 8, 4); MOIHGP_DMA_PROBE(21, 9, 4); MOIHGP_DMA_PROBE(22, 12, 3); MOIHGP_DMA_PROBE(23, 16, 2); MOIHGP_DMA_PROBE(24, 8, 3);
         MOIHGP_DMA_PROBE(25, 12, 2); MOIHGP_DMA_PROBE(26, 8, 2); MOIHGP_DMA_PROBE(27, 20, 2);
 #undef MOIHGP_DMA_PROBE
@@ -1498,11 +1499,11 @@ int launch_filter_stream(int d, int dtype, const void* Ty, size_t T, size_t ld, 
     // many latents (no time split): the LDS-DMA kernel
     if (variant == -1 && nsplit == 1 && MOIHGP_FILTER_DMA) {
         if (dtype == 0) {
-            if (d == 2) return launch_filter_dma_t<double, 2, kChunk64, kDmaRing64, kDmaWaves64>(Ty, T, ld, L, cb64, cb64, xin, x, yhat, nll, stream, ev0, ev1, n_unstable, total, ldo);
-            return launch_filter_dma_t<double, 3, kChunk64, kDmaRing64, kDmaWaves64>(Ty, T, ld, L, cb64, cb64, xin, x, yhat, nll, stream, ev0, ev1, n_unstable, total, ldo);
+            if (d == 2) return launch_filter_dma_t<double, 2, kChunk64, kDmaRing64, kDmaWaves64>(io, cb64, cb64, n_unstable);
+            return launch_filter_dma_t<double, 3, kChunk64, kDmaRing64, kDmaWaves64>(io, cb64, cb64, n_unstable);
         }
-        if (d == 2) return launch_filter_dma_t<float, 2, kChunk32, kDmaRing32, kDmaWaves32>(Ty, T, ld, L, cb32, cb64, xin, x, yhat, nll, stream, ev0, ev1, n_unstable, total, ldo);
-        return launch_filter_dma_t<float, 3, kChunk32, kDmaRing32, kDmaWaves32>(Ty, T, ld, L, cb32, cb64, xin, x, yhat, nll, stream, ev0, ev1, n_unstable, total, ldo);
+        if (d == 2) return launch_filter_dma_t<float, 2, kChunk32, kDmaRing32, kDmaWaves32>(io, cb32, cb64, n_unstable);
+        return launch_filter_dma_t<float, 3, kChunk32, kDmaRing32, kDmaWaves32>(io, cb32, cb64, n_unstable);
     }
     if (dtype == 0) {
         if (d == 2) MOIHGP_FILTER_CASE(double, 2, kChunk64, 1, cb64);

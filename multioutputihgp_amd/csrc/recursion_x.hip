@@ -1888,33 +1888,31 @@ __global__ void __launch_bounds__(1024) sum_slices_total_kernel(const double* __
 }
 
 template <typename T, int DB, int J, int WPB, bool SPLIT>
-int launch_x(const void* Ty, size_t Tlen, size_t ld, size_t L, const T* cbT, const double* cb64, const void* xin, void* x, void* yhat, double* nll,
-             hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, int nslice, int segs_per_slice, double* nll_part, size_t ldo,
-             int* link_flags = nullptr, double* link_state = nullptr, double* total = nullptr,
-             int pass_mode = 0 /* 0: first pass + second (LINKS) pass; 1: the first only; 2: the second only;
-                                    4: the first only, writing predicted observations HA x instead of filtered means (no NLL);
-                                    5: the imputation sweeps of the latents the first pass flagged (filter_x_gaps_a / _b_kernel) */,
-             const GapArgs* ga = nullptr) {
+int launch_x(const SweepIo& io, const T* cbT, const double* cb64, int nslice, int segs_per_slice, double* nll_part,
+             int* link_flags = nullptr, double* link_state = nullptr, StackPass pass = StackPass::Auto, const GapArgs* ga = nullptr) {
+    const size_t Tlen = io.T, ld = io.ld, L = io.L, ldo = io.ld_out;
+    double* const nll = io.nll;
+    const hipStream_t stream = io.stream;
     dim3 block(64 * WPB), grid(SPLIT ? (unsigned)L : (unsigned)((L + WPB - 1) / WPB), SPLIT ? (unsigned)nslice : 1u);
-    const T* ty = static_cast<const T*>(Ty);
-    const T* xi = static_cast<const T*>(xin);
-    T* xs = static_cast<T*>(x);
-    T* yh = static_cast<T*>(yhat);
+    const T* ty = static_cast<const T*>(io.Ty);
+    const T* xi = static_cast<const T*>(io.xin);
+    T* xs = static_cast<T*>(io.x);
+    T* yh = static_cast<T*>(io.yhat);
     if (SPLIT) link_flags = nullptr;
     // (link_flags: zero when the handle allocates them, set by the first pass, cleared again by the second as it takes a latent over)
 #define MOIHGP_X_LAUNCH(W_, N_)                                                                                                              \
     do {                                                                                                                                     \
-        if (pass_mode != 2)                                                                                                                  \
-            hipExtLaunchKernelGGL((filter_x_kernel<T, DB, J, W_, N_, WPB, SPLIT, false>), grid, block, 0, stream, ev0, ev1, 0,                \
+        if (pass != StackPass::SecondOnly)                                                                                                   \
+            hipExtLaunchKernelGGL((filter_x_kernel<T, DB, J, W_, N_, WPB, SPLIT, false>), grid, block, 0, stream, io.ev0, io.ev1, 0,          \
                                   ty, Tlen, ld, L, cbT, cb64, xi, xs, yh, nll, nslice, segs_per_slice, nll_part, ldo, link_flags, link_state); \
         if constexpr (!SPLIT) {                                                                                                              \
-            if (link_flags && (pass_mode == 0 || pass_mode == 2))  /* second pass: the latents stopped at a segment with gaps (none: the grid exits at once) */ \
+            if (link_flags && (pass == StackPass::Auto || pass == StackPass::SecondOnly))  /* second pass: the latents stopped at a segment with gaps (none: the grid exits at once) */ \
                 hipLaunchKernelGGL((filter_x_kernel<T, DB, J, W_, N_, WPB, SPLIT, true>), grid, block, 0, stream,                             \
                                    ty, Tlen, ld, L, cbT, cb64, xi, xs, yh, nll, nslice, segs_per_slice, nll_part, ldo, link_flags, link_state); \
         }                                                                                                                                    \
     } while (0)
     if constexpr (!SPLIT) {
-        if (pass_mode == 4) {
+        if (pass == StackPass::FirstPredicted) {
             hipLaunchKernelGGL((filter_x_kernel<T, DB, J, true, false, WPB, SPLIT, false, true>), grid, block, 0, stream,
                                ty, Tlen, ld, L, cbT, cb64, xi, xs, yh, nll, nslice, segs_per_slice, nll_part, ldo, link_flags, link_state);
             hipError_t e4 = hipGetLastError();
@@ -1922,13 +1920,13 @@ int launch_x(const void* Ty, size_t Tlen, size_t ld, size_t L, const T* cbT, con
             return 0;
         }
         if constexpr (J >= 2) {
-            if (pass_mode == 5) {
+            if (pass == StackPass::Impute) {
                 hipLaunchKernelGGL((filter_x_gaps_a_kernel<T, DB, J, WPB>), grid, block, 0, stream, ty, Tlen, ld, L, cbT, cb64, xi, (const int*)link_flags,
                                    (const double*)link_state, static_cast<const T*>(ga->imp), ga->gpos, static_cast<T*>(ga->gval), static_cast<T*>(ga->gw), ga->gcap, ga->gstat);
 #define MOIHGP_X_GAPS(W_, N_) hipLaunchKernelGGL((filter_x_gaps_b_kernel<T, DB, J, W_, N_, WPB>), grid, block, 0, stream, ty, Tlen, ld, L, cbT, cb64, xi, xs, yh, nll, ldo, \
                                                  link_flags, (const double*)link_state, (const int*)ga->gpos, static_cast<const T*>(ga->gw), ga->gcap, (const int*)ga->gstat)
-                if (yhat && nll) MOIHGP_X_GAPS(true, true);
-                else if (yhat) MOIHGP_X_GAPS(true, false);
+                if (yh && nll) MOIHGP_X_GAPS(true, true);
+                else if (yh) MOIHGP_X_GAPS(true, false);
                 else if (nll) MOIHGP_X_GAPS(false, true);
                 else { set_last_error("the imputation sweep needs an output"); return 1; }
 #undef MOIHGP_X_GAPS
@@ -1938,60 +1936,58 @@ int launch_x(const void* Ty, size_t Tlen, size_t ld, size_t L, const T* cbT, con
             }
         }
     }
-    if (yhat && nll) MOIHGP_X_LAUNCH(true, true);
-    else if (yhat) MOIHGP_X_LAUNCH(true, false);
+    if (yh && nll) MOIHGP_X_LAUNCH(true, true);
+    else if (yh) MOIHGP_X_LAUNCH(true, false);
     else if (nll) MOIHGP_X_LAUNCH(false, true);
     else MOIHGP_X_LAUNCH(false, false);
 #undef MOIHGP_X_LAUNCH
-    if (SPLIT && nll && total) hipLaunchKernelGGL(sum_slices_total_kernel, dim3(1), dim3(1024), 0, stream, nll_part, L, nslice, nll, total);
+    if (SPLIT && nll && io.total) hipLaunchKernelGGL(sum_slices_total_kernel, dim3(1), dim3(1024), 0, stream, nll_part, L, nslice, nll, io.total);
     else if (SPLIT && nll) hipLaunchKernelGGL(sum_slices_kernel, dim3((unsigned)((L + 255) / 256)), dim3(256), 0, stream, nll_part, L, nslice, nll);
-    else if (nll && total) launch_nll_total(nll, L, total, stream);
+    else if (nll && io.total) launch_nll_total(nll, L, io.total, stream);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_last_error("filter_x_kernel launch: %s", hipGetErrorString(e)); return 2; }
     return 0;
 }
 
 template <typename T, int DB, int J>
-int launch_x_team(const void* Ty, size_t Tlen, size_t ld, size_t L, const T* cbT, const double* cb64, const void* xin, void* x, void* yhat, double* nll,
-                  hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, size_t ldo, double* total, int nw) {
+int launch_x_team(const SweepIo& io, const T* cbT, const double* cb64, int nw) {
     const size_t smem = team_smem_bytes<T, DB * J>(nw);
-    dim3 block(64 * nw), grid((unsigned)L);
+    dim3 block(64 * nw), grid((unsigned)io.L);
 #define MOIHGP_TEAM_LAUNCH(W_, N_)                                                                                                                   \
     do {                                                                                                                                             \
         auto kfn = filter_x_team_kernel<T, DB, J, W_, N_>;                                                                                           \
         static size_t attr_set = 48 * 1024;  /* (more dynamic LDS than the default limit needs the attribute: raised on demand, per instantiation) */    \
         if (smem > attr_set) { MOIHGP_HIP_FATAL(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); attr_set = smem; } \
-        hipExtLaunchKernelGGL(kfn, grid, block, smem, stream, ev0, ev1, 0, (const T*)Ty, Tlen, ld, L, cbT, cb64, (const T*)xin, (T*)x, (T*)yhat, nll, ldo, nw); \
+        hipExtLaunchKernelGGL(kfn, grid, block, smem, io.stream, io.ev0, io.ev1, 0, (const T*)io.Ty, io.T, io.ld, io.L, cbT, cb64, (const T*)io.xin, (T*)io.x, (T*)io.yhat, io.nll, io.ld_out, nw); \
     } while (0)
-    if (yhat && nll) MOIHGP_TEAM_LAUNCH(true, true);
-    else if (yhat) MOIHGP_TEAM_LAUNCH(true, false);
-    else if (nll) MOIHGP_TEAM_LAUNCH(false, true);
+    if (io.yhat && io.nll) MOIHGP_TEAM_LAUNCH(true, true);
+    else if (io.yhat) MOIHGP_TEAM_LAUNCH(true, false);
+    else if (io.nll) MOIHGP_TEAM_LAUNCH(false, true);
     else MOIHGP_TEAM_LAUNCH(false, false);
 #undef MOIHGP_TEAM_LAUNCH
-    if (nll && total) launch_nll_total(nll, L, total, stream);
+    if (io.nll && io.total) launch_nll_total(io.nll, io.L, io.total, io.stream);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_last_error("filter_x_team_kernel launch: %s", hipGetErrorString(e)); return 2; }
     return 0;
 }
 
 template <typename T, int DB, int J, int CK>
-int launch_x_teamc(const void* Ty, size_t Tlen, size_t ld, size_t L, const T* cbT, const double* cb64, const T* tpT, const void* xin, void* x, void* yhat, double* nll,
-                   hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, size_t ldo, double* total, int nw) {
+int launch_x_teamc(const SweepIo& io, const T* cbT, const double* cb64, const T* tpT, int nw) {
     const size_t smem = teamc_smem_bytes<T, DB * J, CK>(nw);
-    dim3 block(64 * nw), grid((unsigned)L);
+    dim3 block(64 * nw), grid((unsigned)io.L);
 #define MOIHGP_TEAMC_LAUNCH(W_, N_)                                                                                                                  \
     do {                                                                                                                                             \
         auto kfn = filter_x_teamc_kernel<T, DB, J, W_, N_, CK>;                                                                                      \
         static size_t attr_set = 48 * 1024;                                                                                                          \
         if (smem > attr_set) { MOIHGP_HIP_FATAL(hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); attr_set = smem; } \
-        hipExtLaunchKernelGGL(kfn, grid, block, smem, stream, ev0, ev1, 0, (const T*)Ty, Tlen, ld, L, cbT, cb64, tpT, (const T*)xin, (T*)x, (T*)yhat, nll, ldo, nw); \
+        hipExtLaunchKernelGGL(kfn, grid, block, smem, io.stream, io.ev0, io.ev1, 0, (const T*)io.Ty, io.T, io.ld, io.L, cbT, cb64, tpT, (const T*)io.xin, (T*)io.x, (T*)io.yhat, io.nll, io.ld_out, nw); \
     } while (0)
-    if (yhat && nll) MOIHGP_TEAMC_LAUNCH(true, true);
-    else if (yhat) MOIHGP_TEAMC_LAUNCH(true, false);
-    else if (nll) MOIHGP_TEAMC_LAUNCH(false, true);
+    if (io.yhat && io.nll) MOIHGP_TEAMC_LAUNCH(true, true);
+    else if (io.yhat) MOIHGP_TEAMC_LAUNCH(true, false);
+    else if (io.nll) MOIHGP_TEAMC_LAUNCH(false, true);
     else MOIHGP_TEAMC_LAUNCH(false, false);
 #undef MOIHGP_TEAMC_LAUNCH
-    if (nll && total) launch_nll_total(nll, L, total, stream);
+    if (io.nll && io.total) launch_nll_total(io.nll, io.L, io.total, io.stream);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_last_error("filter_x_teamc_kernel launch: %s", hipGetErrorString(e)); return 2; }
     return 0;
@@ -2016,9 +2012,9 @@ int teamc_blocks_per_cu(int nw, size_t smem, bool w, bool n) {
 // the chunk-templated team kernel for a stream of Tlen ticks, if one of its chunk lengths gives 2 .. kTeamCWaves segments that fit a compute unit
 // (returns -1 if none does: the caller goes on to the other forms)
 template <typename T, int DB, int J>
-int try_x_teamc(const void* Ty, size_t Tlen, size_t ld, size_t L, const T* cbT, const double* cb64, const T* tpT, const void* xin, void* x, void* yhat, double* nll,
-                hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, size_t ldo, double* total, int team_mode) {
+int try_x_teamc(const SweepIo& io, const T* cbT, const double* cb64, const T* tpT, int team_mode) {
     if (!tpT) return -1;
+    const size_t Tlen = io.T, L = io.L;
     if constexpr (ReplayConst<T, DB, J>::PK || ReplayConst<T, DB, J>::SOP) {
         int rc = -1;
         auto attempt = [&](auto ckk) {
@@ -2028,12 +2024,12 @@ int try_x_teamc(const void* Ty, size_t Tlen, size_t ld, size_t L, const T* cbT, 
             if (nw < 2) return;
             const size_t smem = teamc_smem_bytes<T, DB * J, CK>((int)nw);
             if (smem > 150 * 1024) { rc = -2; return; }                                  // (a longer chunk needs more LDS still)
-            const size_t per_cu = (size_t)teamc_blocks_per_cu<T, DB, J, CK>((int)nw, smem, yhat != nullptr, nll != nullptr);
+            const size_t per_cu = (size_t)teamc_blocks_per_cu<T, DB, J, CK>((int)nw, smem, io.yhat != nullptr, io.nll != nullptr);
             // up to TWO rounds of workgroups over the 256 compute units (measured at 10^4 ticks, profiles/r03/midL_team_vs_split.log: d = 3 fp64 at 320 /
             // 384 / 512 latents 17.7 / 18.4 / 20.4 us against 22.7 / 24.0 / 27.0 with the time split, d = 6 fp32 at 512 19.0 against 22.5; three rounds are
             // level, four lose)
             if (!(team_mode == 1 || L <= 2 * 256 * per_cu)) { rc = -2; return; }
-            rc = launch_x_teamc<T, DB, J, CK>(Ty, Tlen, ld, L, cbT, cb64, tpT, xin, x, yhat, nll, stream, ev0, ev1, ldo, total, (int)nw);
+            rc = launch_x_teamc<T, DB, J, CK>(io, cbT, cb64, tpT, (int)nw);
         };
         attempt(std::integral_constant<int, 16>{});
         attempt(std::integral_constant<int, 20>{});
@@ -2047,23 +2043,18 @@ int try_x_teamc(const void* Ty, size_t Tlen, size_t ld, size_t L, const T* cbT, 
 }
 
 template <typename T, int DB, int J>
-int launch_xd(const void* Ty, size_t Tlen, size_t ld, size_t L, const T* cbT, const double* cb64, const void* xin, void* x, void* yhat, double* nll,
-              hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, double* scratch, size_t scratch_len, int force_slices, size_t ldo,
-              int* link_flags, double* link_state, double* total, int env_links, int team_mode, const T* tpT) {
+int launch_xd(const SweepIo& io, const T* cbT, const double* cb64, const StackOpts& opts, const T* tpT) {
     constexpr size_t SEG = 64 * (size_t)kChunkX;
+    const size_t Tlen = io.T, L = io.L;
     if (L >= 1024) {
+        // missing ticks by imputation (capi.cpp): StackPass::FirstAllGaps, ::Impute, ::SecondOnly in turn; ::FirstPredicted for the filters' impulse responses
+        const StackPass pass = opts.pass;
+        if (pass == StackPass::FirstPredicted || pass == StackPass::Impute)
+            return launch_x<T, DB, J, 4, false>(io, cbT, cb64, 1, 0, nullptr, pass == StackPass::Impute ? opts.link_flags : nullptr, opts.link_state, pass, opts.gaps);
         // chunks with a gap per segment up to which the broken-link stages of the second pass beat the tick-by-tick walk (measured,
         // tools/filternan.py: a stage costs one scan + one replay, the second pass of the fp64 d = 12 kernel runs one wave per SIMD)
-        // force_slices < -1 (missing ticks by imputation, filter_x_gaps_a / _b_kernel): -2 = the first pass alone, handing over EVERY latent that holds a
-        // gap; -3 = the second pass alone; -6 = the first pass alone, writing predicted observations HA x instead of filtered means (the filters'
-        // impulse responses); -7 = the imputation sweep of the latents the first pass flagged (scratch then points at a host-side GapArgs)
-        const int pass_mode = force_slices == -2 ? 1 : force_slices == -3 ? 2 : force_slices == -6 ? 4 : force_slices == -7 ? 5 : 0;
-        if (pass_mode >= 4)
-            return launch_x<T, DB, J, 4, false>(Ty, Tlen, ld, L, cbT, cb64, xin, x, yhat, nll, stream, ev0, ev1, 1, 0, nullptr, ldo,
-                                                pass_mode == 5 ? link_flags : nullptr, link_state, nullptr, pass_mode, reinterpret_cast<const GapArgs*>(scratch));
-        const int max_links = pass_mode == 1 ? 64 : (env_links >= 0 ? env_links : (DB * J <= kPairMaxDim ? 64 : ((sizeof(T) == 8 && DB * J > 9) ? 3 : 32)));
-        return launch_x<T, DB, J, 4, false>(Ty, Tlen, ld, L, cbT, cb64, xin, x, yhat, nll, stream, ev0, ev1, 1, max_links, nullptr, ldo,
-                                            (max_links > 0 && link_state) ? link_flags : nullptr, link_state, total, pass_mode);
+        const int max_links = pass == StackPass::FirstAllGaps ? 64 : (opts.max_links >= 0 ? opts.max_links : (DB * J <= kPairMaxDim ? 64 : ((sizeof(T) == 8 && DB * J > 9) ? 3 : 32)));
+        return launch_x<T, DB, J, 4, false>(io, cbT, cb64, 1, max_links, nullptr, (max_links > 0 && opts.link_state) ? opts.link_flags : nullptr, opts.link_state, pass);
     }
     const size_t nseg = (Tlen + SEG - 1) / SEG;
     // few latents, a stream of 2 .. kTeamWaves segments: one workgroup per latent, one wavefront per segment (filter_x_team_kernel), as long as
@@ -2072,23 +2063,27 @@ int launch_xd(const void* Ty, size_t Tlen, size_t ld, size_t L, const T* cbT, co
     // profiles/r03/smallnan_*.log) it is as fast on streams without gaps (d = 12: 18.4 against 17.8-18.4 us, d = 9: 16.9 against 17.1) and
     // four times faster on streams with gaps (350 us against 1300-1700: the split's slices work on a gappy latent side by side, a team
     // kernel walks its segments one after the other, and the chunk-map scan that fixes this up to d = 6 needs a D x D map per lane).
+    int team_mode = opts.team_mode;
     if (team_mode == -1 && DB * J > kPairMaxDim && sizeof(T) == 4) team_mode = 0;
+    const bool automatic = opts.pass == StackPass::Auto && opts.slices == 0;     // (a forced slice count or a single pass: the time split)
     // ... eight wavefronts and the chunk length to match, where the replay takes the chunk length (fp32; fp64 up to d = 8)
     // (team_mode 2 = the 32-tick team kernel only)
-    if (team_mode != 0 && team_mode != 2 && force_slices == 0) {
-        const int rc = try_x_teamc<T, DB, J>(Ty, Tlen, ld, L, cbT, cb64, tpT, xin, x, yhat, nll, stream, ev0, ev1, ldo, total, team_mode);
+    if (team_mode != 0 && team_mode != 2 && automatic) {
+        const int rc = try_x_teamc<T, DB, J>(io, cbT, cb64, tpT, team_mode);
         if (rc != -1) return rc;
     }
-    if (team_mode != 0 && force_slices == 0 && nseg >= 2 && nseg <= (size_t)kTeamWaves) {
+    if (team_mode != 0 && automatic && nseg >= 2 && nseg <= (size_t)kTeamWaves) {
         const size_t smem = team_smem_bytes<T, DB * J>((int)nseg);
         size_t per_cu = (160 * 1024) / smem;
         if (per_cu > 2048 / (64 * nseg)) per_cu = 2048 / (64 * nseg);
         if (smem <= 150 * 1024 && (team_mode == 1 || team_mode == 2 || L <= 256 * per_cu))
-            return launch_x_team<T, DB, J>(Ty, Tlen, ld, L, cbT, cb64, xin, x, yhat, nll, stream, ev0, ev1, ldo, total, (int)nseg);
+            return launch_x_team<T, DB, J>(io, cbT, cb64, (int)nseg);
     }
     // otherwise: one wavefront per workgroup, and the stream cut into time slices (one wavefront each) while that adds
     // wavefronts the chip can still use
-    size_t want = force_slices > 0 ? (size_t)force_slices : (2048 + L - 1) / L;
+    double* const scratch = opts.slice_nll;
+    const size_t scratch_len = opts.slice_nll_len;
+    size_t want = opts.slices > 0 ? (size_t)opts.slices : (2048 + L - 1) / L;
     if (want > nseg) want = nseg;
     if (want * L > scratch_len) want = scratch_len / L;
     if (want < 1) want = 1;                                            // (one slice = the whole stream: same kernel)
@@ -2100,8 +2095,8 @@ int launch_xd(const void* Ty, size_t Tlen, size_t ld, size_t L, const T* cbT, co
         const size_t own_min = per * SEG - (size_t)kChunkX * 32;
         n = 1 + (Tlen - per * SEG + own_min - 1) / own_min;
     }
-    if (n * L > scratch_len) return launch_x<T, DB, J, 1, true>(Ty, Tlen, ld, L, cbT, cb64, xin, x, yhat, nll, stream, ev0, ev1, 1, (int)nseg, scratch, ldo, nullptr, nullptr, total);
-    return launch_x<T, DB, J, 1, true>(Ty, Tlen, ld, L, cbT, cb64, xin, x, yhat, nll, stream, ev0, ev1, (int)n, (int)per, scratch, ldo, nullptr, nullptr, total);
+    if (n * L > scratch_len) return launch_x<T, DB, J, 1, true>(io, cbT, cb64, 1, (int)nseg, scratch);
+    return launch_x<T, DB, J, 1, true>(io, cbT, cb64, (int)n, (int)per, scratch);
 }
 
 }  // namespace
@@ -2109,21 +2104,18 @@ int launch_xd(const void* Ty, size_t Tlen, size_t ld, size_t L, const T* cbT, co
 // this translation unit's model (DB, J) = (MOIHGP_X_TU / 10, MOIHGP_X_TU % 10): both precisions behind one entry (stack_dispatch.hip picks the unit)
 #define MOIHGP_X_CAT2(a_, b_) a_##b_
 #define MOIHGP_X_CAT(a_, b_) MOIHGP_X_CAT2(a_, b_)
-int MOIHGP_X_CAT(launch_filter_x_, MOIHGP_X_TU)(int dtype, const void* Ty, size_t T, size_t ld, size_t L, const double* cb64, const float* cb32,
-                           const void* xin, void* x, void* yhat, double* nll, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1,
-                           double* scratch, size_t scratch_len, int force_slices, size_t ldo, int* link_flags, double* link_state, double* total, int max_links, int team_mode,
-                           const double* tp64, const float* tp32) {
+int MOIHGP_X_CAT(launch_filter_x_, MOIHGP_X_TU)(const SweepIo& io, const double* cb64, const float* cb32, const StackOpts& opts) {
     constexpr int DBB = MOIHGP_X_TU / 10, JJ = MOIHGP_X_TU % 10;
-    if constexpr (JJ == 1) {
-        // the reference's own models (one component); force_slices -1 = the few-latents team kernel or nothing (the caller carries on with recursion.hip)
-        if (force_slices == -1) {
-            if (L == 0 || team_mode == 0) return -1;
-            return dtype == 0 ? try_x_teamc<double, DBB, 1>(Ty, T, ld, L, cb64, cb64, tp64, xin, x, yhat, nll, stream, ev0, ev1, ldo ? ldo : ld, total, team_mode)
-                              : try_x_teamc<float, DBB, 1>(Ty, T, ld, L, cb32, cb64, tp32, xin, x, yhat, nll, stream, ev0, ev1, ldo ? ldo : ld, total, team_mode);
+    if (opts.pass == StackPass::TeamOnly) {
+        if constexpr (JJ == 1) {                         // the reference's own models (one component)
+            if (io.L == 0 || opts.team_mode == 0) return -1;
+            return io.dtype == 0 ? try_x_teamc<double, DBB, 1>(io, cb64, cb64, opts.tp64, opts.team_mode)
+                                 : try_x_teamc<float, DBB, 1>(io, cb32, cb64, opts.tp32, opts.team_mode);
+        } else {
+            return -1;
         }
     }
-    return dtype == 0 ? launch_xd<double, DBB, JJ>(Ty, T, ld, L, cb64, cb64, xin, x, yhat, nll, stream, ev0, ev1, scratch, scratch_len, force_slices, ldo, link_flags, link_state, total, max_links, team_mode, tp64)
-                      : launch_xd<float, DBB, JJ>(Ty, T, ld, L, cb32, cb64, xin, x, yhat, nll, stream, ev0, ev1, scratch, scratch_len, force_slices, ldo, link_flags, link_state, total, max_links, team_mode, tp32);
+    return io.dtype == 0 ? launch_xd<double, DBB, JJ>(io, cb64, cb64, opts, opts.tp64) : launch_xd<float, DBB, JJ>(io, cb32, cb64, opts, opts.tp32);
 }
 
 }  // namespace moihgp

@@ -69,11 +69,7 @@ __global__ void __launch_bounds__(64) team_powers_kernel(const double* __restric
 }  // namespace
 
 // the per-model units (recursion_x.hip compiled with -DMOIHGP_X_TU=DBJ)
-#define MOIHGP_X_DECL(DBJ)                                                                                                                           \
-    int launch_filter_x_##DBJ(int dtype, const void* Ty, size_t T, size_t ld, size_t L, const double* cb64, const float* cb32, const void* xin, void* x, \
-                              void* yhat, double* nll, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, double* scratch, size_t scratch_len,     \
-                              int force_slices, size_t ldo, int* link_flags, double* link_state, double* total, int max_links, int team_mode,       \
-                              const double* tp64, const float* tp32)
+#define MOIHGP_X_DECL(DBJ) int launch_filter_x_##DBJ(const SweepIo& io, const double* cb64, const float* cb32, const StackOpts& opts)
 MOIHGP_X_DECL(21); MOIHGP_X_DECL(31); MOIHGP_X_DECL(22); MOIHGP_X_DECL(23); MOIHGP_X_DECL(24); MOIHGP_X_DECL(32); MOIHGP_X_DECL(33); MOIHGP_X_DECL(34);
 #undef MOIHGP_X_DECL
 
@@ -94,23 +90,20 @@ void launch_team_powers(int kernel, const double* cb64, size_t L, double* tp64, 
     MOIHGP_HIP_FATAL(hipGetLastError());
 }
 
-int launch_filter_teamc_plain(int d, int dtype, const void* Ty, size_t T, size_t ld, size_t L, const double* xc64, const float* xc32, const double* tp64, const float* tp32,
-                              const void* xin, void* x, void* yhat, double* nll, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1, size_t ldo, double* total, int team_mode) {
+int launch_filter_teamc_plain(int d, const SweepIo& io, const double* xc64, const float* xc32, const double* tp64, const float* tp32, int team_mode) {
     if (!xc64 || !tp64) return -1;
-    return d == 2 ? launch_filter_x_21(dtype, Ty, T, ld, L, xc64, xc32, xin, x, yhat, nll, stream, ev0, ev1, nullptr, 0, -1, ldo, nullptr, nullptr, total, -1, team_mode, tp64, tp32)
-                  : launch_filter_x_31(dtype, Ty, T, ld, L, xc64, xc32, xin, x, yhat, nll, stream, ev0, ev1, nullptr, 0, -1, ldo, nullptr, nullptr, total, -1, team_mode, tp64, tp32);
+    StackOpts opts;
+    opts.pass = StackPass::TeamOnly;
+    opts.team_mode = team_mode;
+    opts.tp64 = tp64; opts.tp32 = tp32;
+    return d == 2 ? launch_filter_x_21(io, xc64, xc32, opts) : launch_filter_x_31(io, xc64, xc32, opts);
 }
 
-int launch_filter_stream_x(int kernel, int dtype, const void* Ty, size_t T, size_t ld, size_t L, const double* cb64, const float* cb32,
-                           const void* xin, void* x, void* yhat, double* nll, hipStream_t stream, hipEvent_t ev0, hipEvent_t ev1,
-                           double* scratch, size_t scratch_len, int force_slices, size_t ldo, int* link_flags, double* link_state, double* total, int max_links, int team_mode,
-                           const double* tp64, const float* tp32) {
-    if (L == 0) return 0;
-    if (ldo == 0) ldo = ld;
+int launch_filter_stream_x(int kernel, const SweepIo& io, const double* cb64, const float* cb32, const StackOpts& opts) {
+    if (io.L == 0) return 0;
     const int base = kernel_base(kernel), J = kernel_stack(kernel);
-#define MOIHGP_X_CASE(DBB, JJ)                                                                                        \
-    if (base == (DBB == 2 ? 0 : 1) && J == JJ)                                                                        \
-        return launch_filter_x_##DBB##JJ(dtype, Ty, T, ld, L, cb64, cb32, xin, x, yhat, nll, stream, ev0, ev1, scratch, scratch_len, force_slices, ldo, link_flags, link_state, total, max_links, team_mode, tp64, tp32)
+#define MOIHGP_X_CASE(DBB, JJ) \
+    if (base == (DBB == 2 ? 0 : 1) && J == JJ) return launch_filter_x_##DBB##JJ(io, cb64, cb32, opts)
     MOIHGP_X_CASE(2, 1); MOIHGP_X_CASE(3, 1);            // (the reference's own models in the stacked layout: launch_xc_from_cb)
     MOIHGP_X_CASE(2, 2); MOIHGP_X_CASE(2, 3); MOIHGP_X_CASE(2, 4);
     MOIHGP_X_CASE(3, 2); MOIHGP_X_CASE(3, 3); MOIHGP_X_CASE(3, 4);

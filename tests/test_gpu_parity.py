@@ -1873,6 +1873,51 @@ def test_nll_total_from_the_sweep(env, kern, L, T, dtype):
         tot.fill_(-1.0)
 
 
+PROFILE_ROUTES = [       # the smallest shapes that still take each route of moihgp_filter_stream_io / _tiled
+    ("dma", "Matern52", torch.float32, 1030, 1100, {}),                  # many latents: the LDS-DMA kernel
+    ("dma-segment-major", "Matern52", torch.float32, 1030, 1100, {}),
+    ("team", "Matern52", torch.float64, 3, 5000, {}),                    # few latents: team kernel / time split
+    ("split2", "Matern52", torch.float64, 3, 5000, {"filter_split": 2}),
+    ("stacked", "Matern52x2", torch.float32, 1030, 2100, {}),            # first pass plus second
+    ("stacked-imputed", "Matern52x2", torch.float32, 1030, 2100, {"filter_impute": 1}),   # 1 % NaN: three passes, the pair rides on the first
+    ("stacked-team", "Matern52x2", torch.float64, 3, 2100, {}),
+    ("stacked-split2", "Matern52x2", torch.float64, 3, 2100, {"filter_split": 2}),
+]
+
+
+@pytest.mark.parametrize("route,kern,dtype,L,T,opts", PROFILE_ROUTES, ids=[r[0] for r in PROFILE_ROUTES])
+def test_profile_event_pairs_on_every_route(env, route, kern, dtype, L, T, opts):
+    """moihgp_profile_enable / _read: every sweep carries one event pair around its sweep kernel, whichever route the call takes (bench.py takes
+    every kernel time from them).  Two sweeps give two durations, finite and positive, and -- an event pair brackets part of what the host
+    waited for -- together they are shorter than the wall-clock time of the two calls between two synchronisations."""
+    import time
+    stacked = "x" in kern
+    rng = np.random.default_rng(L + T)
+    prm = synth_params_stacked(L, 2, rng) if stacked else synth_params(L, rng)
+    bank = env["streams"].LatentBank(0.1, prm, kernel=kern if stacked else KMAP[kern])
+    for name, value in opts.items():
+        bank.set_option(name, value)
+    Tyd = to_dev(synth(L, T, rng, nan_frac=0.01 if route == "stacked-imputed" else 0.0), dtype)
+    tiled = route == "dma-segment-major"
+    if tiled:
+        Tyd = env["streams"].tile_stream(Tyd, T)
+    sweep = (lambda: bank.filter_tiled(Tyd, T)) if tiled else (lambda: bank.filter(Tyd, T=T))
+    sweep()                                                     # (first-use allocations and tables stay out of the timed pair)
+    torch.cuda.synchronize()
+    bank.profile_enable(2)
+    t0 = time.perf_counter()
+    for _ in range(2):
+        yhat, _, nll = sweep()
+    torch.cuda.synchronize()
+    wall_ms = (time.perf_counter() - t0) * 1e3
+    ms = bank.profile_read()
+    print(f"{route}: event pairs {ms} ms, wall {wall_ms:.3f} ms")
+    assert yhat is not None and nll is not None
+    assert len(ms) == 2, ms
+    assert all(np.isfinite(v) and v > 0 for v in ms), ms
+    assert sum(ms) < wall_ms, (ms, wall_ms)
+
+
 # ------------------------------------------------------------------------------------------ ordering: sweeps in flight vs update()
 @pytest.mark.parametrize("kernel,J", [("Matern52ss", 0), ("Matern52x4", 4)])
 def test_update_waits_for_sweeps_in_flight(env, kernel, J):
