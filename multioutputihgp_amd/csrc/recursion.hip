@@ -1082,7 +1082,8 @@ __device__ inline bool dma_segment(T* y, T* xin, const DmaConst<T, D, CK>& c, in
 // latent side by side -- instead of series-major [L][ld].  The wavefronts of a launch move through the segments roughly together, so with this
 // layout the chip reads and writes ONE contiguous front, like a plain copy, instead of 4096 row streams 40 KB apart: measured with a copy
 // kernel of the sweep's access pattern (tools/micro/rows_copy.hip, profiles/r04/rows_copy_access_pattern.log) a cold stream moves at
-// 5.7-6.05 TB/s segment-major against 5.0-5.25 TB/s series-major.  `ld` / `ldo` are ignored; the last tile is allocated whole.
+// 5.7-6.05 TB/s segment-major against 5.0-5.25 TB/s series-major.  `ld` / `ldo` are ignored; the last tile is allocated whole, but
+// of its 16-byte vectors only those that hold a tick below T are fetched and stored (960 of 4096 bytes each way are not at T = 10^4, fp32).
 template <typename T, int D, int CK, bool WRITE, bool NLL, int NP, int MINW, bool TILED = false>
 __global__ void __launch_bounds__(64 * kWavesPerBlock, MINW)
 filter_dma_kernel(const T* __restrict__ Ty, size_t Tlen, size_t ld, size_t L, const T* __restrict__ cbT, const double* __restrict__ cb64,
@@ -1127,14 +1128,25 @@ filter_dma_kernel(const T* __restrict__ Ty, size_t Tlen, size_t ld, size_t L, co
     // series-major: this latent's row; segment-major: this latent's tile of segment 0, the tiles of later segments L * 4 KB apart
     const unsigned char* rowb = TILED ? reinterpret_cast<const unsigned char*>(Ty) + l * 4096 : reinterpret_cast<const unsigned char*>(Ty + l * ld);
     const size_t seg_stride = TILED ? L * 4096 : 4096;           // bytes from one segment of this latent to the next
-    // last vector of the row that starts inside the stream (ld >= roundup(T, EPV): it is in bounds); pieces past the end re-read it
+    // last vector of the row that starts inside the stream (ld >= roundup(T, EPV): it is in bounds); pieces past the end re-read it.
+    // Segment-major: the same byte offset counted along the latent's own tiles (its last tile is allocated whole: in bounds as well)
     const size_t lastv = ((Tlen - 1) / EPV) * 16;
     auto issue_piece = [&](size_t p, unsigned slot, bool inside) {
         lds_void_t* dst = (lds_void_t*)(ring + (size_t)slot * 1024);
         if (TILED) {
-            // (the last tile is allocated whole: no clamping inside the stream's segments; pieces past the last segment re-read its last piece)
-            const size_t pp = p < 4 * nseg ? p : 4 * nseg - 1;
-            __builtin_amdgcn_global_load_lds((glb_cvoid_t*)(rowb + (pp >> 2) * seg_stride + (pp & 3) * 1024 + goff), dst, 16, 0, 0);
+            // The last tile is allocated whole, but its ticks past T are nobody's data: a vector that lies wholly past the stream's end -- in
+            // a ragged last tile or in a piece past the last segment -- is not fetched.  As in the series-major rows the lane re-reads the
+            // vector that holds tick T - 1 (one cache line per instruction): lastv, as tile lastv / 4 KB = nseg - 1 and byte lastv % 4 KB
+            if (inside) {
+                __builtin_amdgcn_global_load_lds((glb_cvoid_t*)(rowb + (p >> 2) * seg_stride + (p & 3) * 1024 + goff), dst, 16, 0, 0);
+            } else {
+                const bool past = (p >> 2) >= nseg;                                     // wave-uniform: tile, and the last byte offset to fetch in it
+                const size_t ts = past ? nseg - 1 : (p >> 2);
+                const unsigned lim = ts == nseg - 1 ? (unsigned)(lastv & 4095) : 4080u;
+                unsigned o = past ? lim : (unsigned)(p & 3) * 1024 + goff;
+                o = o < lim ? o : lim;
+                __builtin_amdgcn_global_load_lds((glb_cvoid_t*)(rowb + ts * seg_stride + o), dst, 16, 0, 0);
+            }
         } else if (inside) {
             __builtin_amdgcn_global_load_lds((glb_cvoid_t*)(rowb + p * 1024 + goff), dst, 16, 0, 0);
         } else {
@@ -1191,7 +1203,7 @@ filter_dma_kernel(const T* __restrict__ Ty, size_t Tlen, size_t ld, size_t L, co
     // Running addresses, one step of seg_stride per segment: the tile the refill of this segment fetches (NP / 4 segments ahead) and the tile
     // its results go to, both wave-uniform (the lane's share is goff)
     constexpr bool RING4 = NP % 4 == 0;                        // a segment's four slots are consecutive: slot0, +1, +2, +3, no wrap
-    const size_t nin = TILED ? nseg : nfullp / 4;              // segments whose four pieces are fetched unclamped
+    const size_t nin = nfullp / 4;                             // segments whose four pieces are fetched unclamped: whole ones (T / SEG) in both layouts
     const unsigned char* inb = rowb + (size_t)(NP / 4) * seg_stride;
     unsigned char* outb = orowb;
     // An unstable latent (rho(AKHA) > 1: scan tables overflowed, flagged by IHGP::update) is left to filter_seq_kernel
@@ -1257,10 +1269,14 @@ filter_dma_kernel(const T* __restrict__ Ty, size_t Tlen, size_t ld, size_t L, co
             if constexpr (RING4) lds_read4_kb<AV>(la + slot0 * 1024, o);
             else lds_read4<AV>(la + slot0 * 1024, la + s1 * 1024, la + s2 * 1024, la + s3 * 1024, o);
             unsigned char* po = outb + goff;
-            if (TILED || tbase + SEG <= Tlen) {                  // (a tile is stored whole: its padding belongs to the stream)
+            if (tbase + SEG <= Tlen) {
 #pragma unroll
                 for (int i = 0; i < 4; i++) __builtin_nontemporal_store(o[i], reinterpret_cast<AV*>(po + i * 1024));
             } else {
+                // the ragged last segment, in both layouts (a tile's padding past T is left as it was found): result vector i leaves only if it
+                // holds a tick below T -- tbase sizeof(T) + i 1024 + goff is its byte offset in the stream, i 1024 + goff the one in the row /
+                // the tile.  This is always the wave's last segment: no counted wait follows it, only vmcnt(0), so the number of stores
+                // a lane issues here cannot disturb the count
 #pragma unroll
                 for (int i = 0; i < 4; i++)
                     if (tbase * sizeof(T) + i * 1024 + goff < Tlen * sizeof(T)) __builtin_nontemporal_store(o[i], reinterpret_cast<AV*>(po + i * 1024));
