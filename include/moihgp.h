@@ -307,6 +307,41 @@ int moihgp_forecast_stream(moihgp_gp* gp, int dtype, const void* Ty, size_t T, s
 int moihgp_forecast_tail(moihgp_gp* gp, int dtype, const void* x, size_t n, void* tail, size_t ld_out, void* stream);
 int moihgp_forecast_variances(moihgp_gp* gp, const int* horizons, size_t K, double* var);
 
+/* ---- fixed-lag smoothing of whole streams, with variances (not in the reference) -------------------------------------------------------------
+ * The mean of every latent at tick t given the ticks up to t + l: what an online caller knows about tick t once it has waited l more ticks.  It
+ * is the member of the family between the filtered mean (l = 0: moihgp_forecast_stream with h = 0 and the Kalman gains) and the smoothed one
+ * (l >= T: moihgp_smooth_stream) -- a forecast with a negative horizon.
+ * Per latent, take the smoother's tables A, K, G, P, PF, Ps (moihgp_smooth_stream), S = P_00 + R, and its forward pass:
+ *     xp[t] = A xf[t-1] (xf[-1] = x_in);  p[t] = H xp[t];  v[t] = y[t] - p[t] (0 where y[t] is NaN);  xf[t] = xp[t] + K v[t]
+ * For lags l_0 .. l_{K-1} (0 <= l <= 2^20, 1 <= K <= MOIHGP_LAGGED_MAX_LAGS, need not be sorted or distinct):
+ *     lag[k][l][t] = p[t] + ( sum_{j=0..l_k, t+j<T} G^j K v[t+j] )_0          0 <= t < T
+ *     var[k][l]    = ( Ps + G^l_k (PF - Ps) (G^l_k)^T )_00
+ * i.e. plane k holds, AT THE INDEX OF THE TICK IT ESTIMATES, the mean of the latent at tick t given the ticks <= min(t + l_k, T - 1); an online
+ * caller has it at tick t + l_k.  The variance is the steady-state one of the latent FUNCTION (add R for an observation): var_filtered at l = 0,
+ * falling monotonically to var_smoothed (PF - Ps = sum_{j>=1} G^j (K S K^T) (G^j)^T).  The windowed sum is computed by the exact backward recursion
+ *     s_k[t] = G s_k[t+1] + K v[t] - (G^{l_k+1} K) v[t+l_k+1]      (v = 0 at and past T; s_k[T] = 0),      lag[k][l][t] = p[t] + s_k[t]_0
+ * Missing ticks and the two ends are treated as the smoother treats them: the gains are the steady-state ones, so in the interior of a long gap-free
+ * stream the result is the exact GP conditional mean and variance given y[0 .. t + l]; within a few correlation lengths of the start of the stream
+ * and of missing ticks it is the IHGP approximation.
+ * moihgp_lagged_stream: Ty, x_in, ld_in, ld_out, alignment, asynchrony and stream bookkeeping as moihgp_forecast_stream.  lags: HOST int [K], read
+ *   before the call returns.  ypred [L][ld_out] (dtype) is required and receives p; out holds K planes [L][ld_out], plane k starting k * plane_stride
+ *   elements after out (plane_stride >= L * ld_out and a multiple of 16 bytes).  out, ypred and Ty must be mutually disjoint.  x [L][d] receives the
+ *   FILTERED state after tick T_state - 1, T_state <= T: T_state = T is the ordinary end state, T_state = 0 returns x_in (x may alias x_in).  A stream
+ *   that arrives in slabs is smoothed exactly, without being held whole, by calling on each slab [t0, t1) followed by max(lags) ticks of lookahead
+ *   with T_state = t1 - t0, keeping the first t1 - t0 ticks of every plane and carrying x into the next call.  status: DEVICE int [L] or NULL; a
+ *   latent whose Kalman DARE did not converge gets status 1 and NaN in all its K rows, in its row of ypred and in x.  The smoother's tables are
+ *   built on the first such call after a table rewrite, exactly as by a smooth.  Arithmetic is fp64 for both stream types (an fp32 stream's v is
+ *   rounded once to fp32, its results are narrowed on store).  Returns 1 (and launches nothing) for K or a lag out of range, T_state > T, bad strides or alignment, an
+ *   overlap; 3 for stacked models.
+ *   Option "lagged_path" (moihgp_set_option): -1 automatic (the time-parallel scan kernels; a serial fp64 walk for latents whose G or A - K H A
+ *   fails the smoother's growth bound), 0 scan kernels for every latent, 1 serial fp64 walk for every latent.
+ * moihgp_lagged_variances: var [K][L] to a HOST buffer (NaN for a latent whose Kalman DARE did not converge).  Synchronises. */
+#define MOIHGP_LAGGED_MAX_LAGS 8
+int moihgp_lagged_stream(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x, size_t T_state,
+                         const int* lags, size_t K, void* ypred, void* out, size_t ld_out, size_t plane_stride,
+                         int* status, void* stream);
+int moihgp_lagged_variances(moihgp_gp* gp, const int* lags, size_t K, double* var);
+
 /* ---- seeded steady-state posterior samples of whole streams (not in the reference) -----------------------------------------------------------
  * Joint draws over time of every latent given ALL the ticks of the stream: the smoother's mean plus a stationary deviation process with the
  * steady-state posterior's covariance across time.  The textbook backward sampler (x~[t] = xf[t] + G (x~[t+1] - A xf[t]) + w, w ~ N(0, PF - G P G^T))

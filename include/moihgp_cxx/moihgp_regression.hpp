@@ -231,6 +231,44 @@ public:
         for (size_t t = 0; t < T; t++) for (size_t m = 0; m < M; m++) Yf[t][m] = flat[t * M + m];
         return Yf;
     }
+    // (not in the reference) Fixed-lag smoothing of the series with the current parameters (include/moihgp.h moihgp_lagged_stream): element t is the
+    // mean of every output at tick t given Y[0 .. min(t + lag, T - 1)], from a zero start state -- predictAhead(Y, 0) at lag 0, predictSmoothed(Y)
+    // once lag >= T.  fp64 on the device: project_stream -> lagged_stream -> unproject_stream.  Throws std::invalid_argument for a lag outside
+    // 0 .. 2^20 and std::runtime_error if a latent's Kalman DARE did not converge (status 1: its row would be NaN).  Missing outputs (NaN) are
+    // projected as in predictSmoothed().
+    std::vector<Vector> predictLagged(const std::vector<Vector>& Y, int lag) {
+        if (lag < 0 || lag > (1 << 20)) throw std::invalid_argument("predictLagged: lag must be 0 .. 2^20");
+        const size_t T = Y.size(), M = _num_output, L = _num_latent, ld = (T + 1) / 2 * 2;
+        std::vector<Vector> Yl(T, Vector(M, 0.0));
+        if (T == 0) return Yl;
+        Vector flat(T * M), zeros(L * _dim, 0.0);
+        for (size_t t = 0; t < T; t++) for (size_t m = 0; m < M; m++) flat[t * M + m] = Y[t][m];
+        moihgp_dvec_ctx* ctx = moihgp_dvec_ctx_new();
+        const size_t nst = (L + 1) / 2;                             // status words: L ints in doubles' storage
+        double *dY = moihgp_dvec_alloc(T * M), *dTy = moihgp_dvec_alloc(L * ld), *dyp = moihgp_dvec_alloc(L * ld), *dlg = moihgp_dvec_alloc(L * ld),
+               *dx = moihgp_dvec_alloc(L * _dim), *dst = moihgp_dvec_alloc(nst);
+        int rc = (ctx && dY && dTy && dyp && dlg && dx && dst) ? 0 : 4;
+        Vector st(nst, 0.0);
+        void* s = ctx ? moihgp_dvec_ctx_stream(ctx) : nullptr;
+        moihgp_gp* h = _moihgp->handle();
+        if (!rc) rc = moihgp_dvec_upload(ctx, dY, flat.data(), T * M);
+        if (!rc) rc = moihgp_dvec_upload(ctx, dx, zeros.data(), L * _dim);
+        if (!rc) rc = moihgp_project_stream(h, MOIHGP_F64, dY, T, dTy, ld, s);
+        if (!rc) rc = moihgp_lagged_stream(h, MOIHGP_F64, dTy, T, ld, dx, dx, T, &lag, 1, dyp, dlg, ld, L * ld, reinterpret_cast<int*>(dst), s);
+        if (!rc) rc = moihgp_unproject_stream(h, MOIHGP_F64, dlg, T, ld, dY, s);
+        if (!rc) rc = moihgp_dvec_download(ctx, flat.data(), dY, T * M);
+        if (!rc) rc = moihgp_dvec_download(ctx, st.data(), dst, nst);
+        if (ctx) { moihgp_dvec_sync(ctx); moihgp_release_stream(h, s); }
+        for (double* p : {dY, dTy, dyp, dlg, dx, dst}) if (p) moihgp_dvec_free(p);
+        if (ctx) moihgp_dvec_ctx_del(ctx);
+        if (rc) throw std::runtime_error(std::string("predictLagged: ") + moihgp_last_error());
+        std::vector<int> status(2 * nst, 0);
+        std::memcpy(status.data(), st.data(), sizeof(double) * nst);
+        for (size_t l = 0; l < L; l++)
+            if (status[l] != 0) throw std::runtime_error("predictLagged: the Kalman DARE of latent " + std::to_string(l) + " did not converge");
+        for (size_t t = 0; t < T; t++) for (size_t m = 0; m < M; m++) Yl[t][m] = flat[t * M + m];
+        return Yl;
+    }
     // (not in the reference) predict() as ONE pass over the whole series on the device (include/moihgp.h): project -> filter -> un-project in
     // fp64 from a zero start state, where predict() makes one gp32_step3 round trip per tick; element t is what predict() returns at tick t, to
     // rounding.  tiled = true runs the segment-major entries (moihgp_project_stream_tiled -> moihgp_filter_stream_tiled ->

@@ -143,6 +143,13 @@ struct moihgp_gp {
     hipEvent_t fc_ev = nullptr;
     bool fc_ev_set = false;
     int opt_forecast_path = -1;          // option "forecast_path": -1 automatic, 0 scan kernel, 1 serial fp64
+    // fixed-lag smoothing (moihgp_lagged_stream): the per-call tables, rebuilt by every call for its lags on its stream, with the forecast tables'
+    // event protocol (lt_ev marks the end of the last call that used them)
+    double* dlt = nullptr;
+    hipStream_t lt_last = nullptr;
+    hipEvent_t lt_ev = nullptr;
+    bool lt_ev_set = false;
+    int opt_lagged_path = -1;            // option "lagged_path": -1 automatic, 0 scan kernels, 1 serial fp64
     // posterior sampling (moihgp_sample_stream): the realization's per-latent tables, built lazily behind the smoother's (ensure_sampler)
     LazyTables sp;
     int opt_sample_path = -1;            // option "sample_path": -1 automatic, 0 scan kernel, 1 serial fp64
@@ -152,7 +159,7 @@ struct moihgp_gp {
 
 static void gp_free(moihgp_gp* g) {
     if (!g) return;
-    void* ptrs[] = {g->dU, g->dS, g->dsqrtS, g->dinvsqrtS, g->dsigma, g->dparams, g->cb64, g->cb32, g->dx, g->dpart, g->dTy, g->dUty, g->dTyhat, g->dloss, g->dgrad, g->dscratch, g->dwork, g->dpolar, g->dfallback, g->dwin, g->dunstable, g->dxscratch, g->cbd64, g->dU32, g->dhp, g->dlink, g->dwinmiss, g->dtp64, g->dtp32, g->dxc64, g->dxc32, g->dlinkflags, g->dgap, g->drescue_idx, g->drescue, g->drescue_const, g->sm.d, g->dfc64, g->dfc32, g->sp.d};
+    void* ptrs[] = {g->dU, g->dS, g->dsqrtS, g->dinvsqrtS, g->dsigma, g->dparams, g->cb64, g->cb32, g->dx, g->dpart, g->dTy, g->dUty, g->dTyhat, g->dloss, g->dgrad, g->dscratch, g->dwork, g->dpolar, g->dfallback, g->dwin, g->dunstable, g->dxscratch, g->cbd64, g->dU32, g->dhp, g->dlink, g->dwinmiss, g->dtp64, g->dtp32, g->dxc64, g->dxc32, g->dlinkflags, g->dgap, g->drescue_idx, g->drescue, g->drescue_const, g->sm.d, g->dfc64, g->dfc32, g->sp.d, g->dlt};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (void* p : g->pinned) (void)hipHostUnregister(p);
@@ -165,6 +172,7 @@ static void gp_free(moihgp_gp* g) {
     if (g->sm.ev) (void)hipEventDestroy(g->sm.ev);
     if (g->fc_ev) (void)hipEventDestroy(g->fc_ev);
     if (g->sp.ev) (void)hipEventDestroy(g->sp.ev);
+    if (g->lt_ev) (void)hipEventDestroy(g->lt_ev);
     if (g->stream) (void)hipStreamDestroy(g->stream);
     delete g;
 }
@@ -1208,6 +1216,82 @@ int moihgp_forecast_variances(moihgp_gp* gp, const int* horizons, size_t K, doub
     return guard_rc([&] { return forecast_variances_impl(gp, horizons, K, var); });
 }
 
+// ---- fixed-lag smoothing (lagged.hip) ------------------------------------------------------------------------------------------------------------
+// The tables depend on the call's lags, so every call builds them on its own stream into the handle's buffer, as the forecasts do.
+static void lagged_begin(moihgp_gp* g, hipStream_t s) {
+    if (!g->dlt) g->dlt = dev_alloc<double>(g->L * (size_t)lt_size(g->d));
+    if (!g->lt_ev) MOIHGP_HIP_FATAL(hipEventCreateWithFlags(&g->lt_ev, hipEventDisableTiming));
+    if (g->lt_ev_set && s != g->lt_last) MOIHGP_HIP_FATAL(hipStreamWaitEvent(s, g->lt_ev, 0));
+}
+static void lagged_end(moihgp_gp* g, hipStream_t s) {
+    g->lt_last = s;
+    g->lt_ev_set = true;
+    MOIHGP_HIP_FATAL(hipEventRecord(g->lt_ev, s));
+}
+
+static int check_lags(const int* lags, size_t K, LagList& ll) {
+    if (K < 1 || K > (size_t)MOIHGP_LAGGED_MAX_LAGS) { set_last_error("lagged: the number of lags (%zu) must be 1 .. %d", K, MOIHGP_LAGGED_MAX_LAGS); return 1; }
+    if (!lags) { set_last_error("lagged: null lags"); return 1; }
+    for (size_t k = 0; k < (size_t)kLagMaxLags; k++) ll.lag[k] = 0;
+    for (size_t k = 0; k < K; k++) {
+        if (lags[k] < 0 || lags[k] > (1 << 20)) { set_last_error("lagged: lag %zu (%d) must be 0 .. 2^20", k, lags[k]); return 1; }
+        ll.lag[k] = lags[k];
+    }
+    return 0;
+}
+
+static int lagged_stream_impl(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x, size_t T_state, const int* lags,
+                              size_t K, void* ypred, void* out, size_t ld_out, size_t plane_stride, int* status, void* stream) {
+    if (int rc = check_sweep_call(gp, dtype, Ty, T, ld_in, x_in, x)) return rc;
+    LagList ll;
+    if (int rc = check_lags(lags, K, ll)) return rc;
+    if (T_state > T) { set_last_error("lagged: T_state (%zu) must be <= T (%zu)", T_state, T); return 1; }
+    const size_t es = dtype == MOIHGP_F64 ? 8 : 4;
+    if (int rc = check_out_rows(ypred, "ypred", T, 'T', ld_out, es)) return rc;
+    if (int rc = check_out_rows(out, "lag buffer", T, 'T', ld_out, es)) return rc;
+    if (int rc = check_planes(out, plane_stride, gp->L, ld_out, es)) return rc;
+    // the backward sweep reads y and the predicted means to the right of the ticks it writes: the three may not overlap
+    const size_t out_elems = (K - 1) * plane_stride + gp->L * ld_out;
+    if (int rc = check_no_overlap(Ty, gp->L * ld_in, ypred, gp->L * ld_out, T, es, "ypred must not overlap the input stream")) return rc;
+    if (int rc = check_no_overlap(Ty, gp->L * ld_in, out, out_elems, T, es, "the lag buffer must not overlap the input stream")) return rc;
+    if (int rc = check_no_overlap(ypred, gp->L * ld_out, out, out_elems, T, es, "the lag buffer must not overlap ypred")) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = ensure_smoother(gp, s)) return rc;
+    note_user_stream(gp, s);
+    lagged_begin(gp, s);
+    launch_lagged_tables(gp->d, gp->sm.d, gp->L, ll, (int)K, gp->dlt, s);
+    launch_lagged_stream(gp->d, dtype, Ty, T, ld_in, gp->L, gp->sm.d, gp->dlt, x_in, x, T_state, ll, (int)K, ypred, out, ld_out, plane_stride, status,
+                         gp->opt_lagged_path, s);
+    lagged_end(gp, s);
+    return 0;
+}
+
+static int lagged_variances_impl(moihgp_gp* gp, const int* lags, size_t K, double* var) {
+    if (!gp) { set_last_error("null handle"); return 1; }
+    LagList ll;
+    if (int rc = check_lags(lags, K, ll)) return rc;
+    if (int rc = ensure_smoother(gp, gp->stream)) return rc;
+    if (!var) return 0;
+    lagged_begin(gp, gp->stream);
+    launch_lagged_tables(gp->d, gp->sm.d, gp->L, ll, (int)K, gp->dlt, gp->stream);
+    const size_t bs = (size_t)lt_size(gp->d), vo = (size_t)(gp->d == 2 ? LT<2>::VAR : LT<3>::VAR);
+    std::vector<double> b(gp->L * bs);
+    MOIHGP_HIP_FATAL(hipMemcpyAsync(b.data(), gp->dlt, sizeof(double) * b.size(), hipMemcpyDeviceToHost, gp->stream));
+    lagged_end(gp, gp->stream);
+    MOIHGP_HIP_FATAL(hipStreamSynchronize(gp->stream));
+    for (size_t k = 0; k < K; k++)
+        for (size_t l = 0; l < gp->L; l++) var[k * gp->L + l] = b[l * bs + vo + k];
+    return 0;
+}
+
+int moihgp_lagged_stream(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x, size_t T_state, const int* lags,
+                         size_t K, void* ypred, void* out, size_t ld_out, size_t plane_stride, int* status, void* stream) {
+    return guard_rc([&] { return lagged_stream_impl(gp, dtype, Ty, T, ld_in, x_in, x, T_state, lags, K, ypred, out, ld_out, plane_stride, status, stream); });
+}
+int moihgp_lagged_variances(moihgp_gp* gp, const int* lags, size_t K, double* var) {
+    return guard_rc([&] { return lagged_variances_impl(gp, lags, K, var); });
+}
+
 // ---- seeded steady-state posterior sampling (sampler.hip) ---------------------------------------------------------------------------------------
 // The realization's tables follow the smoother's, by the same protocol (ensure_tables).  The rewrites themselves do nothing for them.
 static int ensure_sampler(moihgp_gp* g, hipStream_t s) {
@@ -1602,6 +1686,7 @@ int moihgp_release_stream(moihgp_gp* gp, void* stream) {
             MOIHGP_HIP_FATAL(hipStreamWaitEvent(gp->stream, gp->order_ev, 0));
             gp->user_streams.erase(gp->user_streams.begin() + (long)i);
             if (gp->fc_last == s) gp->fc_last = gp->stream;   // (the handle's stream now follows s: a later forecast on any other stream waits for fc_ev)
+            if (gp->lt_last == s) gp->lt_last = gp->stream;   // (the same for the fixed-lag tables and lt_ev)
             break;
         }
         return 0;
@@ -1619,6 +1704,7 @@ int moihgp_set_option(moihgp_gp* gp, const char* name, long value) {
     if (n == "filter_maxlinks") { if (value < -1 || value > 64) { set_last_error("filter_maxlinks: -1 (automatic) .. 64"); return 1; } gp->opt_filter_maxlinks = (int)value; return 0; }
     if (n == "sample_path") { if (value < -1 || value > 1) { set_last_error("sample_path: -1 (automatic), 0 (scan kernel), 1 (serial fp64)"); return 1; } gp->opt_sample_path = (int)value; return 0; }
     if (n == "smoother_path") { if (value < -1 || value > 1) { set_last_error("smoother_path: -1 (automatic), 0 (scan kernels), 1 (serial fp64)"); return 1; } gp->opt_smoother_path = (int)value; return 0; }
+    if (n == "lagged_path") { if (value < -1 || value > 1) { set_last_error("lagged_path: -1 (automatic), 0 (scan kernels), 1 (serial fp64)"); return 1; } gp->opt_lagged_path = (int)value; return 0; }
     if (n == "forecast_path") { if (value < -1 || value > 1) { set_last_error("forecast_path: -1 (automatic), 0 (scan kernel), 1 (serial fp64)"); return 1; } gp->opt_forecast_path = (int)value; return 0; }
     if (n == "filter_variant") {
 #ifdef MOIHGP_TUNING

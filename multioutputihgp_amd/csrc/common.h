@@ -233,6 +233,10 @@ void launch_smoother_tables(int kernel, int d, const double* cb64, size_t L, dou
 // path: -1 automatic (scan kernels for the latents that pass the growth bound), 0 scan kernels, 1 serial fp64 for every latent
 void launch_smooth_stream(int d, int dtype, const void* Ty, size_t T, size_t ld_in, size_t L, const double* tabs, const void* x_in, void* x,
                           void* ys, size_t ld_out, int* status, int path, hipStream_t stream);
+// the smoother's forward sweep alone, for the fixed-lag smoother: predicted means into p [L][ld_out], and into x the filtered state after tick
+// T_state - 1 (T_state <= T; 0: x_in), for the latents the scan kernels take (and the NaN row and state of a failed one)
+void launch_smooth_forward(int d, int dtype, const void* Ty, size_t T, size_t ld_in, size_t L, const double* tabs, const void* x_in, void* x,
+                           size_t T_state, void* p, size_t ld_out, int path, hipStream_t stream);
 // forecast.hip: multi-horizon forecasts (include/moihgp.h moihgp_forecast_stream).  Per-latent block FT<D> of fc_size(d) scalars (stream_tables.h), built
 // per call for the call's horizons, as an fp64 and an fp32 copy; sm: the smoother's blocks (gains 0: Kalman-form K, A - K H A, PF) or unused (gains 1: the handle's).
 constexpr int kFcMaxHorizons = 8;   // MOIHGP_FORECAST_MAX_HORIZONS
@@ -243,6 +247,15 @@ void launch_forecast_tables(int kernel, int d, const double* cb64, const double*
 void launch_forecast_stream(int d, int dtype, const void* Ty, size_t T, size_t ld_in, size_t L, const double* t64, const float* t32, const void* x_in,
                             void* x, void* fc, size_t ld_out, size_t plane_stride, int K, int* status, int path, hipStream_t stream);
 void launch_forecast_tail(int d, int dtype, const double* cb64, size_t L, const void* x, size_t n, void* tail, size_t ld_out, hipStream_t stream);
+// lagged.hip: fixed-lag smoothing (include/moihgp.h moihgp_lagged_stream).  Per-latent fp64 block LT<D> of lt_size(d) doubles (stream_tables.h), built per
+// call for the call's lags from the smoother's blocks sm, which the sweeps read beside it.  ypred [L][ld_out] receives the forward pass's predicted
+// means, out the K planes; x the filtered state after tick T_state - 1.  path as launch_smooth_stream's.
+constexpr int kLagMaxLags = 8;   // MOIHGP_LAGGED_MAX_LAGS
+struct LagList { int lag[kLagMaxLags]; };
+void launch_lagged_tables(int d, const double* sm, size_t L, const LagList& lags, int K, double* lt, hipStream_t stream);
+void launch_lagged_stream(int d, int dtype, const void* Ty, size_t T, size_t ld_in, size_t L, const double* sm, const double* lt, const void* x_in,
+                          void* x, size_t T_state, const LagList& lags, int K, void* ypred, void* out, size_t ld_out, size_t plane_stride, int* status,
+                          int path, hipStream_t stream);
 // sampler.hip: seeded steady-state posterior samples (include/moihgp.h moihgp_sample_stream).  Per-latent fp64 block SP<D> of sp_size(d) doubles
 // (stream_tables.h) from the smoother's blocks sm; ysm: the smoothed means [L][ld_out] the deviations are added to; samples [S][L][ld_out], planes
 // plane_stride apart.  path as launch_smooth_stream's.  status: 0 ok, 1 Kalman DARE failed, 2 realization failed (sample rows NaN).

@@ -1,5 +1,5 @@
 // scan_sweep.h -- device machinery of the chunk-scan sweeps over whole streams (smoother.hip: smooth_fwd_kernel, smooth_bwd_kernel;
-// forecast.hip: forecast_sweep_kernel; sampler.hip: sample_sweep_kernel).  One wavefront per latent walks the stream in segments of
+// forecast.hip: forecast_sweep_kernel; sampler.hip: sample_sweep_kernel; lagged.hip: lagged_bwd_kernel).  One wavefront per latent walks the stream in segments of
 // 64 x kScanChunk ticks staged through LDS (coalesced in and out): each lane takes kScanChunk consecutive ticks, computes its chunk's affine map
 // from a zero state, a Kogge-Stone scan of the maps over the 64 lanes gives every lane its true start state, and the lane replays its chunk from
 // there.  Both directions live here: forward in time (chunk_map, lane 0 first) and backward (chunk_response_bwd, lane 63 first, a chunk walked
@@ -131,12 +131,12 @@ __device__ __forceinline__ void chunk_map(const Ta* y, int n, bool regular, cons
 
 // Backward: the response r of the whole chunk e[0 .. kScanChunk) under s <- G s + K e[i], walked from its last tick to its first from a zero
 // state at its end (the recursion is time-invariant, so the chunk's map is a power of G that the caller holds; entries past the stream's end
-// are zero, come first and leave the state zero)
-template <typename Ta, int D>
-__device__ __forceinline__ void chunk_response_bwd(const Ta* e, const Ta* G, const Ta* K, Ta* r) {
+// are zero, come first and leave the state zero).  Te: the scalar the chunk is staged in (the fixed-lag sweep stages fp32 streams in fp32).
+template <typename Ta, int D, typename Te = Ta>
+__device__ __forceinline__ void chunk_response_bwd(const Te* e, const Ta* G, const Ta* K, Ta* r) {
 #pragma unroll
     for (int i = 0; i < D; i++) r[i] = 0;
-    for (int i = kScanChunk - 1; i >= 0; i--) tick_step<Ta, D>(G, K, e[i], r);
+    for (int i = kScanChunk - 1; i >= 0; i--) tick_step<Ta, D>(G, K, (Ta)e[i], r);
 }
 
 // Inclusive Kogge-Stone scan of affine maps (Phi, r) over the wavefront.  FWD: lane j ends with the composition of lanes 0..j (lane 0 first);

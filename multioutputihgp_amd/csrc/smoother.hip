@@ -17,6 +17,7 @@
 //                            takes kScanChunk consecutive ticks, computes its chunk's affine map from a zero state, a Kogge-Stone scan of the
 //                            maps over the 64 lanes gives every lane its true start state, and the lane replays its chunk writing p[t].
 //                            Missing ticks (x <- A x) and the ragged tail (identity) make a lane's map its own product of tick maps.
+//                            Its STATE_AT instance is the forward pass of the fixed-lag smoother (lagged.hip, launch_smooth_forward).
 //   smooth_bwd_kernel        the same from the last segment to the first with the lane order mirrored: the map of every chunk is G^kScanChunk
 //                            (the backward recursion is time-invariant even across missing ticks, v = 0 there; ticks past T carry v = 0
 //                            into s[T] = 0, which is exact).  Reads y and p, writes ys (which may alias p).
@@ -31,9 +32,11 @@
 namespace moihgp {
 namespace {
 
-template <typename Tv, int D>
+// STATE_AT (the fixed-lag smoother's forward pass): x_out receives the filtered state after tick T_state - 1 (<= T; 0: x_in), from the replay of
+// the lane that holds that tick, instead of the state that leaves the last segment.  A smooth is the instance without it.
+template <typename Tv, int D, bool STATE_AT>
 __global__ void __launch_bounds__(64) smooth_fwd_kernel(const Tv* __restrict__ Ty, size_t T, size_t ld_in, const double* __restrict__ tabs,
-                                                        const Tv* x_in, Tv* x_out, Tv* __restrict__ p_out, size_t ld_out, int path) {
+                                                        const Tv* x_in, Tv* x_out, Tv* __restrict__ p_out, size_t ld_out, int path, size_t T_state) {
     using B = SM<D>;
     constexpr int NN = D * D;
     __shared__ double buf[kScanPlane];
@@ -53,6 +56,9 @@ __global__ void __launch_bounds__(64) smooth_fwd_kernel(const Tv* __restrict__ T
     double xseg[D];
 #pragma unroll
     for (int i = 0; i < D; i++) xseg[i] = (double)x_in[l * D + i];
+    if (STATE_AT && T_state == 0 && lane == 0)
+#pragma unroll
+        for (int i = 0; i < D; i++) x_out[l * D + i] = (Tv)xseg[i];
     double* my = buf + lane * kScanPitch;
     for (size_t seg0 = 0; seg0 < T; seg0 += kScanSeg) {
         stage_in(yrow, seg0, T, lane, buf);
@@ -73,12 +79,15 @@ __global__ void __launch_bounds__(64) smooth_fwd_kernel(const Tv* __restrict__ T
 #pragma unroll
             for (int j = 0; j < D; j++) xs[j] = fma(K[j], v, xp[j]);
             my[i] = p;
+            if (STATE_AT && seg0 + (size_t)lane * kScanChunk + i + 1 == T_state)
+#pragma unroll
+                for (int j = 0; j < D; j++) x_out[l * D + j] = (Tv)xs[j];
         }
         __syncthreads();
         stage_out(buf, prow, seg0, T, lane);
         __syncthreads();
     }
-    if (lane == 0)
+    if (!STATE_AT && lane == 0)
 #pragma unroll
         for (int i = 0; i < D; i++) x_out[l * D + i] = (Tv)xseg[i];
 }
@@ -319,7 +328,7 @@ template <typename Tv, int D>
 static void launch_smooth_t(const Tv* Ty, size_t T, size_t ld_in, size_t L, const double* tabs, const Tv* x_in, Tv* x, Tv* ys, size_t ld_out,
                             int* status, int path, hipStream_t stream) {
     if (T > 0 && path != 1) {
-        hipLaunchKernelGGL((smooth_fwd_kernel<Tv, D>), dim3((unsigned)L), dim3(64), 0, stream, Ty, T, ld_in, tabs, x_in, x, ys, ld_out, path);
+        hipLaunchKernelGGL((smooth_fwd_kernel<Tv, D, false>), dim3((unsigned)L), dim3(64), 0, stream, Ty, T, ld_in, tabs, x_in, x, ys, ld_out, path, T);
         MOIHGP_HIP_FATAL(hipGetLastError());
         hipLaunchKernelGGL((smooth_bwd_kernel<Tv, D>), dim3((unsigned)L), dim3(64), 0, stream, Ty, T, ld_in, tabs, ys, ld_out, path);
         MOIHGP_HIP_FATAL(hipGetLastError());
@@ -336,6 +345,17 @@ void launch_smooth_stream(int d, int dtype, const void* Ty, size_t T, size_t ld_
         using Tv = decltype(tv);
         launch_smooth_t<Tv, decltype(dim)::value>((const Tv*)Ty, T, ld_in, L, tabs, (const Tv*)x_in, (Tv*)x, (Tv*)ys, ld_out, status, path, stream);
     });
+}
+
+void launch_smooth_forward(int d, int dtype, const void* Ty, size_t T, size_t ld_in, size_t L, const double* tabs, const void* x_in, void* x,
+                           size_t T_state, void* p, size_t ld_out, int path, hipStream_t stream) {
+    if (L == 0 || T == 0) return;
+    dispatch_stream(d, dtype, [&](auto tv, auto dim) {
+        using Tv = decltype(tv);
+        hipLaunchKernelGGL((smooth_fwd_kernel<Tv, decltype(dim)::value, true>), dim3((unsigned)L), dim3(64), 0, stream, (const Tv*)Ty, T, ld_in, tabs,
+                           (const Tv*)x_in, (Tv*)x, (Tv*)p, ld_out, path, T_state);
+    });
+    MOIHGP_HIP_FATAL(hipGetLastError());
 }
 
 }  // namespace moihgp

@@ -1,4 +1,4 @@
-// stream_tables.h -- the per-latent table blocks of the whole-stream smoother (smoother.hip), forecasts (forecast.hip) and sampler (sampler.hip), the
+// stream_tables.h -- the per-latent table blocks of the whole-stream smoother (smoother.hip), forecasts (forecast.hip), fixed-lag smoother (lagged.hip) and sampler (sampler.hip), the
 // chunk geometry their chunk powers are built for, and the (d, dtype) dispatch of their launchers.  Read by those files and by capi.cpp.
 #pragma once
 #include "common.h"
@@ -35,6 +35,15 @@ struct FT {
     static constexpr int SIZE = (STATUS + 1 + 3) / 4 * 4;
 };
 
+// per-latent fixed-lag block (fp64), offsets in doubles, next to the latent's SM<D> block (which holds G, G^kScanChunk, K and the growth figure)
+template <int D>
+struct LT {
+    static constexpr int W = 0;                                       // [kLagMaxLags][D]  w_k = G^(l_k + 1) K (rows past the call's K are zero)
+    static constexpr int VAR = W + kLagMaxLags * D;                   // [kLagMaxLags]
+    static constexpr int STATUS = VAR + kLagMaxLags;
+    static constexpr int SIZE = (STATUS + 1 + 1) / 2 * 2;
+};
+
 // per-latent sampler block (fp64), offsets in doubles: the innovations realization of the smoother's steady-state autocovariance (sampler.hip),
 // next to the latent's SM<D> block (which holds G, G^kScanChunk and Ps)
 template <int D>
@@ -51,6 +60,7 @@ struct SP {
 constexpr int sm_size(int d) { return d == 2 ? SM<2>::SIZE : SM<3>::SIZE; }
 constexpr int fc_size(int d) { return d == 2 ? FT<2>::SIZE : FT<3>::SIZE; }
 constexpr int sp_size(int d) { return d == 2 ? SP<2>::SIZE : SP<3>::SIZE; }
+constexpr int lt_size(int d) { return d == 2 ? LT<2>::SIZE : LT<3>::SIZE; }
 
 // f(std::integral_constant<int, D>) for the state dimension d (2 or 3); f(Tv(), std::integral_constant<int, D>) for the stream's scalar too
 template <typename F>

@@ -102,6 +102,23 @@ def _forecast_horizons(horizons):
     return (C.c_int * len(hs))(*[int(h) for h in hs]), len(hs)
 
 
+LAGGED_MAX_LAGS = 8             # MOIHGP_LAGGED_MAX_LAGS
+
+
+def _lagged_lags(lags):
+    """(ctypes int array, K) of a fixed-lag smoother's lags, validated as include/moihgp.h states them."""
+    try:
+        ls = [h for h in lags]
+    except TypeError:
+        raise ValueError("lags must be a sequence of 1 .. 8 integers") from None
+    if not 1 <= len(ls) <= LAGGED_MAX_LAGS:
+        raise ValueError(f"the number of lags ({len(ls)}) must be 1 .. {LAGGED_MAX_LAGS}")
+    for h in ls:
+        if isinstance(h, bool) or not isinstance(h, (int, np.integer)) or h < 0 or h > (1 << 20):
+            raise ValueError(f"lag {h!r} must be an integer in 0 .. 2^20")
+    return (C.c_int * len(ls))(*[int(h) for h in ls]), len(ls)
+
+
 def _forecast_gains(gains) -> int:
     if gains not in _GAINS:
         raise ValueError('gains must be "kalman" or "handle"')
@@ -449,6 +466,57 @@ class LatentBank:
         _check(rc, self._lib)
         return out, x, status
 
+    def lagged(self, Ty: torch.Tensor, lags, T: Optional[int] = None, x: Optional[torch.Tensor] = None, x_start: Optional[torch.Tensor] = None,
+               state_at: Optional[int] = None, out: Optional[torch.Tensor] = None, ypred: Optional[torch.Tensor] = None, stream=None):
+        """Fixed-lag smoothing of T ticks for every latent (include/moihgp.h moihgp_lagged_stream): lag[k, l, t] is the mean of latent l at tick t
+        given the ticks <= min(t + lags[k], T - 1), stored at the tick it estimates, with the smoother's steady-state gains.  lags: 1 .. 8 ints in
+        0 .. 2^20, in any order; lag 0 is forecast([0]) (the filtered mean), a lag >= T is smooth(); lagged_variances() gives the variances.
+
+        Returns (lag [K, L, >=T], ypred [L, >=T] the one-step predicted means, x [L, d], status [L] int32: 0 ok, 1 Kalman DARE not converged
+        (rows, ypred row and x NaN)).  Asynchronous on the current torch stream.  The sweep starts from `x_start` if given, else from `x`, else from
+        zeros; `x` receives in place the filtered state after tick `state_at` - 1 (default T: the end state; 0: the start state).  A stream that
+        arrives in slabs: call on slab [t0, t1) plus max(lags) ticks of lookahead with `x_start` the carried state and `state_at` = t1 - t0, keep the
+        first t1 - t0 ticks of every plane and carry `x`.  `out` (optional) [K, L, >=T] as forecast()'s, `ypred` (optional) as smooth()'s
+        `ysmooth`; `out`, `ypred` and Ty must not overlap each other."""
+        T, ld = self._check_stream(Ty, T)
+        lg, K = _lagged_lags(lags)
+        state_at = T if state_at is None else state_at
+        if isinstance(state_at, bool) or not isinstance(state_at, (int, np.integer)) or not 0 <= state_at <= T:
+            raise ValueError(f"state_at {state_at!r} must be an integer in 0 .. T")
+        if self.stacked:
+            raise MoihgpError("lagged: stacked models are not supported (Matern-3/2 and -5/2 only)", 3)
+        x, start = self._start_state(Ty, x, x_start)
+        if out is None:
+            ypred, ld_out = self._ysmooth_buffer(Ty, T, ypred)
+            out = torch.empty((K, self.L, ld_out), dtype=Ty.dtype, device=Ty.device)[:, :, :T]
+        ld_out, plane = _plane_out_strides(out, K, self.L, T, Ty)
+        # one row stride serves both buffers in the C entry (as in sample()): a caller's `ypred` of another stride receives a copy
+        yp_user = None
+        if ypred is None:
+            ypred = torch.empty((self.L, ld_out), dtype=Ty.dtype, device=Ty.device)[:, :T]
+        elif self._ysmooth_buffer(Ty, T, ypred)[1] != ld_out and self.L > 1:
+            yp_user, ypred = ypred, torch.empty((self.L, ld_out), dtype=Ty.dtype, device=Ty.device)[:, :T]
+        status = torch.empty((self.L,), dtype=torch.int32, device=Ty.device)
+        rc = self._lib.moihgp_lagged_stream(self._h, _DT[Ty.dtype], C.c_void_p(Ty.data_ptr()), T, ld,
+                                            C.c_void_p(start.data_ptr()), C.c_void_p(x.data_ptr()), int(state_at), lg, K,
+                                            C.c_void_p(ypred.data_ptr()), C.c_void_p(out.data_ptr()), ld_out, plane,
+                                            C.c_void_p(status.data_ptr()), _stream_ptr(stream))
+        _check(rc, self._lib)
+        if yp_user is not None:
+            with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
+                yp_user[:, :T].copy_(ypred)
+            ypred = yp_user
+        return out, ypred, x, status
+
+    def lagged_variances(self, lags) -> np.ndarray:
+        """var [K, L] (moihgp_lagged_variances), fp64 numpy: the steady-state variance of the latent function at tick t given the ticks <= t + lag
+        (add the noise parameter for an observation): var_filtered at lag 0, falling to var_smoothed; NaN for a latent whose Kalman DARE did not
+        converge."""
+        lg, K = _lagged_lags(lags)
+        var = np.zeros((K, self.L))
+        _check(self._lib.moihgp_lagged_variances(self._h, lg, K, var.ctypes.data_as(c_double_p)), self._lib)
+        return var
+
     def forecast_tail(self, x: torch.Tensor, n: int, stream=None) -> torch.Tensor:
         """tail[l, j] = H A^(j+1) x_l, 0 <= j < n (moihgp_forecast_tail): the forecast beyond the end of a stream from its end state x [L, d]."""
         n = int(n)
@@ -660,3 +728,28 @@ def forecast_outputs(gp, Y: torch.Tensor, horizons, tail: int = 0, gains: str = 
     prm = gp.params
     U, S = prm[:M * L].reshape(M, L), prm[M * L:M * L + L]
     return Yf, (S[None, :] * var) @ (U ** 2).T, Ytail
+
+
+def lagged_outputs(gp, Y: torch.Tensor, lags, stream=None):
+    """Fixed-lag smoothed outputs of a tick-major observation stream Y [T, M] (NaN = missing output) with the parameters of `gp` (a
+    pywrapper.MOIHGP), from a zero state: project_stream -> LatentBank.lagged -> unproject_stream per lag.
+
+    Returns (Yl [K, T, M] in Y's dtype, var_Y [K, M] fp64 numpy).  Yl[k, t] is the mean of the outputs at tick t given the ticks
+    <= min(t + lags[k], T - 1).  var_Y[k, m] = sum_l U[m, l]^2 S_l var[k, l]: the steady-state variance of the latent FUNCTION at output m, without
+    the observation noise.  Raises MoihgpError if any latent's Kalman DARE did not converge.  Ticks with missing outputs are projected as
+    project_stream does it: a tick with more than 64 missing outputs or fewer than L observed ones is treated as missing as a whole."""
+    T = Y.shape[0]
+    bank = LatentBank.from_handle(gp)
+    _, K = _lagged_lags(lags)
+    Ty = project_stream(gp, Y, stream=stream)
+    lg, _, _, status = bank.lagged(Ty, lags, T=T, stream=stream)
+    Yl = torch.stack([unproject_stream(gp, lg[k], T, stream=stream) for k in range(K)])
+    var = bank.lagged_variances(lags)      # (synchronises)
+    bad = int(((status != 0).cpu().numpy() | np.isnan(var).any(axis=0)).sum())
+    if bad:
+        raise MoihgpError(f"lagged_outputs: the Kalman DARE of {bad} latent(s) did not converge; their rows and variances are NaN and so is "
+                          "every output that mixes them", 1)
+    M, L = gp.num_output, gp.num_latent
+    prm = gp.params
+    U, S = prm[:M * L].reshape(M, L), prm[M * L:M * L + L]
+    return Yl, (S[None, :] * var) @ (U ** 2).T
