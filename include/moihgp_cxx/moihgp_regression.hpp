@@ -118,36 +118,13 @@ public:
     // projection, which has limits predict() does not: a tick with more than 64 missing outputs, or fewer than num_latent observed ones, is
     // treated as missing as a whole (the smoother then carries the state across it).
     std::vector<Vector> predictSmoothed(const std::vector<Vector>& Y) {
-        const size_t T = Y.size(), M = _num_output, L = _num_latent, ld = (T + 1) / 2 * 2;
-        std::vector<Vector> Ys(T, Vector(M, 0.0));
-        if (T == 0) return Ys;
-        Vector flat(T * M), zeros(L * _dim, 0.0);
-        for (size_t t = 0; t < T; t++) for (size_t m = 0; m < M; m++) flat[t * M + m] = Y[t][m];
-        moihgp_dvec_ctx* ctx = moihgp_dvec_ctx_new();
-        const size_t nst = (L + 1) / 2;                             // status words: L ints in doubles' storage
-        double *dY = moihgp_dvec_alloc(T * M), *dTy = moihgp_dvec_alloc(L * ld), *dys = moihgp_dvec_alloc(L * ld), *dx = moihgp_dvec_alloc(L * _dim),
-               *dst = moihgp_dvec_alloc(nst);
-        int rc = (ctx && dY && dTy && dys && dx && dst) ? 0 : 4;
-        Vector st(nst, 0.0);
-        void* s = ctx ? moihgp_dvec_ctx_stream(ctx) : nullptr;
-        moihgp_gp* h = _moihgp->handle();
-        if (!rc) rc = moihgp_dvec_upload(ctx, dY, flat.data(), T * M);
-        if (!rc) rc = moihgp_dvec_upload(ctx, dx, zeros.data(), L * _dim);
-        if (!rc) rc = moihgp_project_stream(h, MOIHGP_F64, dY, T, dTy, ld, s);
-        if (!rc) rc = moihgp_smooth_stream(h, MOIHGP_F64, dTy, T, ld, dx, dx, dys, ld, reinterpret_cast<int*>(dst), s);
-        if (!rc) rc = moihgp_unproject_stream(h, MOIHGP_F64, dys, T, ld, dY, s);
-        if (!rc) rc = moihgp_dvec_download(ctx, flat.data(), dY, T * M);
-        if (!rc) rc = moihgp_dvec_download(ctx, st.data(), dst, nst);
-        if (ctx) { moihgp_dvec_sync(ctx); moihgp_release_stream(h, s); }
-        for (double* p : {dY, dTy, dys, dx, dst}) if (p) moihgp_dvec_free(p);
-        if (ctx) moihgp_dvec_ctx_del(ctx);
-        if (rc) throw std::runtime_error(std::string("predictSmoothed: ") + moihgp_last_error());
-        std::vector<int> status(2 * nst, 0);
-        std::memcpy(status.data(), st.data(), sizeof(double) * nst);
-        for (size_t l = 0; l < L; l++)
-            if (status[l] != 0) throw std::runtime_error("predictSmoothed: the Kalman DARE of latent " + std::to_string(l) + " did not converge");
-        for (size_t t = 0; t < T; t++) for (size_t m = 0; m < M; m++) Ys[t][m] = flat[t * M + m];
-        return Ys;
+        const size_t T = Y.size(), L = _num_latent, ld = (T + 1) / 2 * 2;
+        if (T == 0) return std::vector<Vector>();
+        return streamRoundTrip("predictSmoothed", Y, {L * ld, L * ld}, [&](StreamTrip& d) {
+            int rc = d.project();
+            if (!rc) rc = moihgp_smooth_stream(d.h, MOIHGP_F64, d.buf[0], T, ld, d.x, d.x, d.buf[1], ld, d.status, d.s);
+            return rc ? rc : d.fetch(d.buf[1]);
+        }, [](size_t l, int) { return "the Kalman DARE of latent " + std::to_string(l) + " did not converge"; })[0];
     }
     // (not in the reference) Seeded joint posterior samples of the whole series with the current parameters (include/moihgp.h
     // moihgp_sample_stream): element [s][t] is sample s of every output at tick t given ALL of Y -- the smoothed mean of predictSmoothed() plus a
@@ -157,40 +134,17 @@ public:
     // (1 Kalman DARE not converged, 2 sampling realization not accepted).  Missing outputs (NaN) are projected as in predictSmoothed().
     std::vector<std::vector<Vector>> sampleSmoothed(const std::vector<Vector>& Y, size_t nsamples, unsigned long long seed = 0) {
         if (nsamples < 1 || nsamples > 65535) throw std::invalid_argument("sampleSmoothed: nsamples must be 1 .. 65535");
-        const size_t T = Y.size(), M = _num_output, L = _num_latent, ld = (T + 1) / 2 * 2, S = nsamples;
-        std::vector<std::vector<Vector>> Ys(S, std::vector<Vector>(T, Vector(M, 0.0)));
-        if (T == 0) return Ys;
-        Vector flat(T * M), zeros(L * _dim, 0.0);
-        for (size_t t = 0; t < T; t++) for (size_t m = 0; m < M; m++) flat[t * M + m] = Y[t][m];
-        moihgp_dvec_ctx* ctx = moihgp_dvec_ctx_new();
-        const size_t nst = (L + 1) / 2;                             // status words: L ints in doubles' storage
-        double *dY = moihgp_dvec_alloc(T * M), *dTy = moihgp_dvec_alloc(L * ld), *dys = moihgp_dvec_alloc(L * ld), *dsm = moihgp_dvec_alloc(S * L * ld),
-               *dx = moihgp_dvec_alloc(L * _dim), *dst = moihgp_dvec_alloc(nst);
-        int rc = (ctx && dY && dTy && dys && dsm && dx && dst) ? 0 : 4;
-        Vector st(nst, 0.0);
-        void* s = ctx ? moihgp_dvec_ctx_stream(ctx) : nullptr;
-        moihgp_gp* h = _moihgp->handle();
-        if (!rc) rc = moihgp_dvec_upload(ctx, dY, flat.data(), T * M);
-        if (!rc) rc = moihgp_dvec_upload(ctx, dx, zeros.data(), L * _dim);
-        if (!rc) rc = moihgp_project_stream(h, MOIHGP_F64, dY, T, dTy, ld, s);
-        if (!rc) rc = moihgp_sample_stream(h, MOIHGP_F64, dTy, T, ld, dx, dx, S, seed, 0, 0, dys, ld, dsm, L * ld, reinterpret_cast<int*>(dst), s);
-        if (!rc) rc = moihgp_dvec_download(ctx, st.data(), dst, nst);
-        for (size_t k = 0; k < S && !rc; k++) {
-            rc = moihgp_unproject_stream(h, MOIHGP_F64, dsm + k * L * ld, T, ld, dY, s);
-            if (!rc) rc = moihgp_dvec_download(ctx, flat.data(), dY, T * M);
-            if (!rc) rc = moihgp_dvec_sync(ctx);
-            if (!rc) for (size_t t = 0; t < T; t++) for (size_t m = 0; m < M; m++) Ys[k][t][m] = flat[t * M + m];
-        }
-        if (ctx) { moihgp_dvec_sync(ctx); moihgp_release_stream(h, s); }
-        for (double* p : {dY, dTy, dys, dsm, dx, dst}) if (p) moihgp_dvec_free(p);
-        if (ctx) moihgp_dvec_ctx_del(ctx);
-        if (rc) throw std::runtime_error(std::string("sampleSmoothed: ") + moihgp_last_error());
-        std::vector<int> status(2 * nst, 0);
-        std::memcpy(status.data(), st.data(), sizeof(double) * nst);
-        for (size_t l = 0; l < L; l++)
-            if (status[l] != 0) throw std::runtime_error("sampleSmoothed: latent " + std::to_string(l) + " has status " + std::to_string(status[l]) +
-                                                         (status[l] == 1 ? " (the Kalman DARE did not converge)" : " (the sampling realization was not accepted)"));
-        return Ys;
+        const size_t T = Y.size(), L = _num_latent, ld = (T + 1) / 2 * 2, S = nsamples;
+        if (T == 0) return std::vector<std::vector<Vector>>(S);
+        return streamRoundTrip("sampleSmoothed", Y, {L * ld, L * ld, S * L * ld}, [&](StreamTrip& d) {
+            int rc = d.project();
+            if (!rc) rc = moihgp_sample_stream(d.h, MOIHGP_F64, d.buf[0], T, ld, d.x, d.x, S, seed, 0, 0, d.buf[1], ld, d.buf[2], L * ld, d.status, d.s);
+            for (size_t k = 0; k < S && !rc; k++) rc = d.fetch(d.buf[2] + k * L * ld);
+            return rc;
+        }, [](size_t l, int status) {
+            return "latent " + std::to_string(l) + " has status " + std::to_string(status) +
+                   (status == 1 ? " (the Kalman DARE did not converge)" : " (the sampling realization was not accepted)");
+        });
     }
     // (not in the reference) Forecasts `horizon` ticks ahead at every tick of the series with the current parameters (include/moihgp.h
     // moihgp_forecast_stream, Kalman-form gains): element t is the mean of every output at tick t + horizon given Y[0..t], from a zero start
@@ -199,37 +153,13 @@ public:
     // if a latent's Kalman DARE did not converge (status 1: its row would be NaN).  Missing outputs (NaN) are projected as in predictSmoothed().
     std::vector<Vector> predictAhead(const std::vector<Vector>& Y, int horizon) {
         if (horizon < 0 || horizon > (1 << 20)) throw std::invalid_argument("predictAhead: horizon must be 0 .. 2^20");
-        const size_t T = Y.size(), M = _num_output, L = _num_latent, ld = (T + 1) / 2 * 2;
-        std::vector<Vector> Yf(T, Vector(M, 0.0));
-        if (T == 0) return Yf;
-        Vector flat(T * M), zeros(L * _dim, 0.0);
-        for (size_t t = 0; t < T; t++) for (size_t m = 0; m < M; m++) flat[t * M + m] = Y[t][m];
-        moihgp_dvec_ctx* ctx = moihgp_dvec_ctx_new();
-        const size_t nst = (L + 1) / 2;                             // status words: L ints in doubles' storage
-        double *dY = moihgp_dvec_alloc(T * M), *dTy = moihgp_dvec_alloc(L * ld), *dfc = moihgp_dvec_alloc(L * ld), *dx = moihgp_dvec_alloc(L * _dim),
-               *dst = moihgp_dvec_alloc(nst);
-        int rc = (ctx && dY && dTy && dfc && dx && dst) ? 0 : 4;
-        Vector st(nst, 0.0);
-        void* s = ctx ? moihgp_dvec_ctx_stream(ctx) : nullptr;
-        moihgp_gp* h = _moihgp->handle();
-        if (!rc) rc = moihgp_dvec_upload(ctx, dY, flat.data(), T * M);
-        if (!rc) rc = moihgp_dvec_upload(ctx, dx, zeros.data(), L * _dim);
-        if (!rc) rc = moihgp_project_stream(h, MOIHGP_F64, dY, T, dTy, ld, s);
-        if (!rc) rc = moihgp_forecast_stream(h, MOIHGP_F64, dTy, T, ld, dx, dx, &horizon, 1, dfc, ld, L * ld, MOIHGP_GAINS_KALMAN,
-                                             reinterpret_cast<int*>(dst), s);
-        if (!rc) rc = moihgp_unproject_stream(h, MOIHGP_F64, dfc, T, ld, dY, s);
-        if (!rc) rc = moihgp_dvec_download(ctx, flat.data(), dY, T * M);
-        if (!rc) rc = moihgp_dvec_download(ctx, st.data(), dst, nst);
-        if (ctx) { moihgp_dvec_sync(ctx); moihgp_release_stream(h, s); }
-        for (double* p : {dY, dTy, dfc, dx, dst}) if (p) moihgp_dvec_free(p);
-        if (ctx) moihgp_dvec_ctx_del(ctx);
-        if (rc) throw std::runtime_error(std::string("predictAhead: ") + moihgp_last_error());
-        std::vector<int> status(2 * nst, 0);
-        std::memcpy(status.data(), st.data(), sizeof(double) * nst);
-        for (size_t l = 0; l < L; l++)
-            if (status[l] != 0) throw std::runtime_error("predictAhead: the Kalman DARE of latent " + std::to_string(l) + " did not converge");
-        for (size_t t = 0; t < T; t++) for (size_t m = 0; m < M; m++) Yf[t][m] = flat[t * M + m];
-        return Yf;
+        const size_t T = Y.size(), L = _num_latent, ld = (T + 1) / 2 * 2;
+        if (T == 0) return std::vector<Vector>();
+        return streamRoundTrip("predictAhead", Y, {L * ld, L * ld}, [&](StreamTrip& d) {
+            int rc = d.project();
+            if (!rc) rc = moihgp_forecast_stream(d.h, MOIHGP_F64, d.buf[0], T, ld, d.x, d.x, &horizon, 1, d.buf[1], ld, L * ld, MOIHGP_GAINS_KALMAN, d.status, d.s);
+            return rc ? rc : d.fetch(d.buf[1]);
+        }, [](size_t l, int) { return "the Kalman DARE of latent " + std::to_string(l) + " did not converge"; })[0];
     }
     // (not in the reference) Fixed-lag smoothing of the series with the current parameters (include/moihgp.h moihgp_lagged_stream): element t is the
     // mean of every output at tick t given Y[0 .. min(t + lag, T - 1)], from a zero start state -- predictAhead(Y, 0) at lag 0, predictSmoothed(Y)
@@ -238,36 +168,13 @@ public:
     // projected as in predictSmoothed().
     std::vector<Vector> predictLagged(const std::vector<Vector>& Y, int lag) {
         if (lag < 0 || lag > (1 << 20)) throw std::invalid_argument("predictLagged: lag must be 0 .. 2^20");
-        const size_t T = Y.size(), M = _num_output, L = _num_latent, ld = (T + 1) / 2 * 2;
-        std::vector<Vector> Yl(T, Vector(M, 0.0));
-        if (T == 0) return Yl;
-        Vector flat(T * M), zeros(L * _dim, 0.0);
-        for (size_t t = 0; t < T; t++) for (size_t m = 0; m < M; m++) flat[t * M + m] = Y[t][m];
-        moihgp_dvec_ctx* ctx = moihgp_dvec_ctx_new();
-        const size_t nst = (L + 1) / 2;                             // status words: L ints in doubles' storage
-        double *dY = moihgp_dvec_alloc(T * M), *dTy = moihgp_dvec_alloc(L * ld), *dyp = moihgp_dvec_alloc(L * ld), *dlg = moihgp_dvec_alloc(L * ld),
-               *dx = moihgp_dvec_alloc(L * _dim), *dst = moihgp_dvec_alloc(nst);
-        int rc = (ctx && dY && dTy && dyp && dlg && dx && dst) ? 0 : 4;
-        Vector st(nst, 0.0);
-        void* s = ctx ? moihgp_dvec_ctx_stream(ctx) : nullptr;
-        moihgp_gp* h = _moihgp->handle();
-        if (!rc) rc = moihgp_dvec_upload(ctx, dY, flat.data(), T * M);
-        if (!rc) rc = moihgp_dvec_upload(ctx, dx, zeros.data(), L * _dim);
-        if (!rc) rc = moihgp_project_stream(h, MOIHGP_F64, dY, T, dTy, ld, s);
-        if (!rc) rc = moihgp_lagged_stream(h, MOIHGP_F64, dTy, T, ld, dx, dx, T, &lag, 1, dyp, dlg, ld, L * ld, reinterpret_cast<int*>(dst), s);
-        if (!rc) rc = moihgp_unproject_stream(h, MOIHGP_F64, dlg, T, ld, dY, s);
-        if (!rc) rc = moihgp_dvec_download(ctx, flat.data(), dY, T * M);
-        if (!rc) rc = moihgp_dvec_download(ctx, st.data(), dst, nst);
-        if (ctx) { moihgp_dvec_sync(ctx); moihgp_release_stream(h, s); }
-        for (double* p : {dY, dTy, dyp, dlg, dx, dst}) if (p) moihgp_dvec_free(p);
-        if (ctx) moihgp_dvec_ctx_del(ctx);
-        if (rc) throw std::runtime_error(std::string("predictLagged: ") + moihgp_last_error());
-        std::vector<int> status(2 * nst, 0);
-        std::memcpy(status.data(), st.data(), sizeof(double) * nst);
-        for (size_t l = 0; l < L; l++)
-            if (status[l] != 0) throw std::runtime_error("predictLagged: the Kalman DARE of latent " + std::to_string(l) + " did not converge");
-        for (size_t t = 0; t < T; t++) for (size_t m = 0; m < M; m++) Yl[t][m] = flat[t * M + m];
-        return Yl;
+        const size_t T = Y.size(), L = _num_latent, ld = (T + 1) / 2 * 2;
+        if (T == 0) return std::vector<Vector>();
+        return streamRoundTrip("predictLagged", Y, {L * ld, L * ld, L * ld}, [&](StreamTrip& d) {
+            int rc = d.project();
+            if (!rc) rc = moihgp_lagged_stream(d.h, MOIHGP_F64, d.buf[0], T, ld, d.x, d.x, T, &lag, 1, d.buf[1], d.buf[2], ld, L * ld, d.status, d.s);
+            return rc ? rc : d.fetch(d.buf[2]);
+        }, [](size_t l, int) { return "the Kalman DARE of latent " + std::to_string(l) + " did not converge"; })[0];
     }
     // (not in the reference) predict() as ONE pass over the whole series on the device (include/moihgp.h): project -> filter -> un-project in
     // fp64 from a zero start state, where predict() makes one gp32_step3 round trip per tick; element t is what predict() returns at tick t, to
@@ -279,36 +186,21 @@ public:
     // projects any tick with at least one observed output.  Stacked models refuse tiled = true (std::runtime_error, the library's return
     // code 3): their sweep takes series-major streams only.
     std::vector<Vector> predictStream(const std::vector<Vector>& Y, bool tiled = false) {
-        const size_t T = Y.size(), M = _num_output, L = _num_latent, seg = 512 /* fp64 ticks per tile */;
+        const size_t T = Y.size(), L = _num_latent, seg = 512 /* fp64 ticks per tile */;
         const size_t ld = (T + 1) / 2 * 2, n = tiled ? (T + seg - 1) / seg * L * seg : L * ld;
-        std::vector<Vector> Yhat(T, Vector(M, 0.0));
-        if (T == 0) return Yhat;
-        Vector flat(T * M), zeros(L * _dim, 0.0);
-        for (size_t t = 0; t < T; t++) for (size_t m = 0; m < M; m++) flat[t * M + m] = Y[t][m];
-        moihgp_dvec_ctx* ctx = moihgp_dvec_ctx_new();
-        double *dY = moihgp_dvec_alloc(T * M), *dTy = moihgp_dvec_alloc(n), *dyh = moihgp_dvec_alloc(n), *dx = moihgp_dvec_alloc(L * _dim);
-        int rc = (ctx && dY && dTy && dyh && dx) ? 0 : 4;
-        void* s = ctx ? moihgp_dvec_ctx_stream(ctx) : nullptr;
-        moihgp_gp* h = _moihgp->handle();
-        if (!rc) rc = moihgp_dvec_upload(ctx, dY, flat.data(), T * M);
-        if (!rc) rc = moihgp_dvec_upload(ctx, dx, zeros.data(), L * _dim);
-        if (tiled) {
-            if (!rc) rc = moihgp_project_stream_tiled(h, MOIHGP_F64, dY, T, dTy, s);
-            if (!rc) rc = moihgp_filter_stream_tiled(h, MOIHGP_F64, dTy, T, dx, dx, dyh, nullptr, nullptr, s);
-            if (!rc) rc = moihgp_unproject_stream_tiled(h, MOIHGP_F64, dyh, T, dY, s);
-        } else {
-            if (!rc) rc = moihgp_project_stream(h, MOIHGP_F64, dY, T, dTy, ld, s);
-            if (!rc) rc = moihgp_filter_stream_v2(h, MOIHGP_F64, dTy, T, ld, dx, dx, dyh, ld, nullptr, nullptr, s);
-            if (!rc) rc = moihgp_unproject_stream(h, MOIHGP_F64, dyh, T, ld, dY, s);
-        }
-        if (!rc) rc = moihgp_dvec_download(ctx, flat.data(), dY, T * M);
-        const std::string err = rc ? moihgp_last_error() : "";
-        if (ctx) { moihgp_dvec_sync(ctx); moihgp_release_stream(h, s); }
-        for (double* p : {dY, dTy, dyh, dx}) if (p) moihgp_dvec_free(p);
-        if (ctx) moihgp_dvec_ctx_del(ctx);
-        if (rc) throw std::runtime_error("predictStream: " + err);
-        for (size_t t = 0; t < T; t++) for (size_t m = 0; m < M; m++) Yhat[t][m] = flat[t * M + m];
-        return Yhat;
+        if (T == 0) return std::vector<Vector>();
+        return streamRoundTrip("predictStream", Y, {n, n}, [&](StreamTrip& d) {
+            int rc;
+            if (tiled) {
+                rc = moihgp_project_stream_tiled(d.h, MOIHGP_F64, d.Y, T, d.buf[0], d.s);
+                if (!rc) rc = moihgp_filter_stream_tiled(d.h, MOIHGP_F64, d.buf[0], T, d.x, d.x, d.buf[1], nullptr, nullptr, d.s);
+                if (!rc) rc = moihgp_unproject_stream_tiled(d.h, MOIHGP_F64, d.buf[1], T, d.Y, d.s);
+                return rc ? rc : d.take();
+            }
+            rc = d.project();
+            if (!rc) rc = moihgp_filter_stream_v2(d.h, MOIHGP_F64, d.buf[0], T, ld, d.x, d.x, d.buf[1], ld, nullptr, nullptr, d.s);
+            return rc ? rc : d.fetch(d.buf[1]);
+        }, [](size_t, int) { return std::string(); })[0];      // (the filter reports no status: the words stay zero)
     }
     Vector getParams() { return _moihgp->getParams(); }
     size_t getNumParam() { return _num_param; }
@@ -320,6 +212,62 @@ public:
     RegressionObjective<StateSpace>& objective() { return *_obj; }   // (not in the reference)
 
 private:
+    // One device round trip of the whole-stream methods above, as its sweep sees it: the handle, the context's stream, and the device vectors --
+    // Y [T][M] the observations, x [L][dim] a zero start state, status L zeroed ints, buf[] the vectors the call named by size (buf[0]: the stream).
+    // Every call of take() adds one [T][M] plane to the method's result.
+    struct StreamTrip {
+        moihgp_gp* h; moihgp_dvec_ctx* ctx; void* s;
+        size_t T, M, ld;
+        double *Y, *x; int* status;
+        std::vector<double*> buf;
+        Vector flat;
+        std::vector<std::vector<Vector>> planes;
+        int project() { return moihgp_project_stream(h, MOIHGP_F64, Y, T, buf[0], ld, s); }          // Y -> buf[0], series-major rows of ld
+        int take() {                                                                                  // Y -> the next plane of the result
+            if (int rc = moihgp_dvec_download(ctx, flat.data(), Y, T * M)) return rc;
+            planes.push_back(std::vector<Vector>(T, Vector(M)));
+            for (size_t t = 0; t < T; t++) for (size_t m = 0; m < M; m++) planes.back()[t][m] = flat[t * M + m];
+            return 0;
+        }
+        int fetch(const double* rows) {                                                               // un-project series-major rows, then take()
+            const int rc = moihgp_unproject_stream(h, MOIHGP_F64, rows, T, ld, Y, s);
+            return rc ? rc : take();
+        }
+    };
+    // The round trip itself, fp64 from a zero start state: flatten Y, create the context and the device vectors (Y, x, the status words, and one per
+    // entry of `sizes`, in doubles), upload, run sweep(trip) -- which projects, issues the method's sweep and takes the result plane by plane --
+    // download the status words, free everything on every path, then throw: on a non-zero return code with moihgp_last_error() as it stood when
+    // the failure was seen (the cleanup calls may overwrite it), on a non-zero status word of latent l with statusText(l, word).
+    template <typename Sweep, typename StatusText>
+    std::vector<std::vector<Vector>> streamRoundTrip(const char* who, const std::vector<Vector>& Y, std::initializer_list<size_t> sizes, Sweep&& sweep,
+                                                     StatusText&& statusText) {
+        const size_t T = Y.size(), M = _num_output, L = _num_latent, nst = (L + 1) / 2;               // status words: L ints in doubles' storage
+        StreamTrip d{_moihgp->handle(), moihgp_dvec_ctx_new(), nullptr, T, M, (T + 1) / 2 * 2, nullptr, nullptr, nullptr, {}, Vector(T * M), {}};
+        for (size_t t = 0; t < T; t++) for (size_t m = 0; m < M; m++) d.flat[t * M + m] = Y[t][m];
+        Vector zeros(L * _dim, 0.0), st(nst, 0.0);
+        std::vector<double*> all = {d.Y = moihgp_dvec_alloc(T * M), d.x = moihgp_dvec_alloc(L * _dim), moihgp_dvec_alloc(nst)};
+        d.status = reinterpret_cast<int*>(all[2]);
+        for (size_t n : sizes) { d.buf.push_back(moihgp_dvec_alloc(n)); all.push_back(d.buf.back()); }
+        int rc = d.ctx ? 0 : 4;
+        for (double* p : all) if (!p) rc = 4;
+        if (d.ctx) d.s = moihgp_dvec_ctx_stream(d.ctx);
+        if (!rc) rc = moihgp_dvec_upload(d.ctx, d.Y, d.flat.data(), T * M);
+        if (!rc) rc = moihgp_dvec_upload(d.ctx, d.x, zeros.data(), L * _dim);
+        if (!rc) rc = moihgp_dvec_upload(d.ctx, all[2], st.data(), nst);
+        if (!rc) rc = sweep(d);
+        if (!rc) rc = moihgp_dvec_download(d.ctx, st.data(), all[2], nst);
+        const std::string err = rc ? moihgp_last_error() : "";
+        if (d.ctx) { moihgp_dvec_sync(d.ctx); moihgp_release_stream(d.h, d.s); }
+        for (double* p : all) if (p) moihgp_dvec_free(p);
+        if (d.ctx) moihgp_dvec_ctx_del(d.ctx);
+        if (rc) throw std::runtime_error(std::string(who) + ": " + err);
+        std::vector<int> status(2 * nst, 0);
+        std::memcpy(status.data(), st.data(), sizeof(double) * nst);
+        for (size_t l = 0; l < L; l++)
+            if (status[l] != 0) throw std::runtime_error(std::string(who) + ": " + statusText(l, status[l]));
+        return std::move(d.planes);
+    }
+
     MOIHGP<StateSpace>* _moihgp;
     bool _threading;
     double _dt;

@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <exception>
+#include <functional>
 #include <random>
 #include <string>
 #include <vector>
@@ -52,6 +53,17 @@ struct LazyTables {
     unsigned long long version = 0;   // cb_version they were built for (0: never)
     hipStream_t built_on = nullptr;   // stream that carried the last build; ev marks its end for the other streams / host reads
     hipEvent_t ev = nullptr;
+};
+
+// Per-latent device tables that depend on a call's own list (a forecast's horizons and gains, a fixed-lag smoother's lags): every call builds them
+// on its own stream into the handle's buffer(s) (call_tables_begin); ev marks the end of the last call that used them (call_tables_end), and a call
+// on another stream waits for it before it rewrites them.
+struct CallTables {
+    double* d64 = nullptr;
+    float* d32 = nullptr;             // the fp32 copy, where the sweep reads one (forecasts)
+    hipStream_t last = nullptr;
+    hipEvent_t ev = nullptr;
+    bool ev_set = false;
 };
 
 struct moihgp_gp {
@@ -135,20 +147,11 @@ struct moihgp_gp {
     // steady-state RTS smoother (moihgp_smooth_stream): its per-latent tables, built lazily on the first smooth after a table rewrite
     LazyTables sm;
     int opt_smoother_path = -1;          // option "smoother_path": -1 automatic, 0 scan kernels, 1 serial fp64
-    // multi-horizon forecasts (moihgp_forecast_stream): the per-call tables (fp64 and fp32 copy), rebuilt by every call for its horizons on its
-    // stream; fc_ev marks the end of the last call that used them, and a call on another stream waits for it before it rewrites them
-    double* dfc64 = nullptr;
-    float* dfc32 = nullptr;
-    hipStream_t fc_last = nullptr;
-    hipEvent_t fc_ev = nullptr;
-    bool fc_ev_set = false;
+    // multi-horizon forecasts (moihgp_forecast_stream): the per-call tables (fp64 and fp32 copy), rebuilt by every call for its horizons
+    CallTables fc;
     int opt_forecast_path = -1;          // option "forecast_path": -1 automatic, 0 scan kernel, 1 serial fp64
-    // fixed-lag smoothing (moihgp_lagged_stream): the per-call tables, rebuilt by every call for its lags on its stream, with the forecast tables'
-    // event protocol (lt_ev marks the end of the last call that used them)
-    double* dlt = nullptr;
-    hipStream_t lt_last = nullptr;
-    hipEvent_t lt_ev = nullptr;
-    bool lt_ev_set = false;
+    // fixed-lag smoothing (moihgp_lagged_stream): the per-call tables (fp64 alone), rebuilt by every call for its lags
+    CallTables lt;
     int opt_lagged_path = -1;            // option "lagged_path": -1 automatic, 0 scan kernels, 1 serial fp64
     // posterior sampling (moihgp_sample_stream): the realization's per-latent tables, built lazily behind the smoother's (ensure_sampler)
     LazyTables sp;
@@ -159,7 +162,7 @@ struct moihgp_gp {
 
 static void gp_free(moihgp_gp* g) {
     if (!g) return;
-    void* ptrs[] = {g->dU, g->dS, g->dsqrtS, g->dinvsqrtS, g->dsigma, g->dparams, g->cb64, g->cb32, g->dx, g->dpart, g->dTy, g->dUty, g->dTyhat, g->dloss, g->dgrad, g->dscratch, g->dwork, g->dpolar, g->dfallback, g->dwin, g->dunstable, g->dxscratch, g->cbd64, g->dU32, g->dhp, g->dlink, g->dwinmiss, g->dtp64, g->dtp32, g->dxc64, g->dxc32, g->dlinkflags, g->dgap, g->drescue_idx, g->drescue, g->drescue_const, g->sm.d, g->dfc64, g->dfc32, g->sp.d, g->dlt};
+    void* ptrs[] = {g->dU, g->dS, g->dsqrtS, g->dinvsqrtS, g->dsigma, g->dparams, g->cb64, g->cb32, g->dx, g->dpart, g->dTy, g->dUty, g->dTyhat, g->dloss, g->dgrad, g->dscratch, g->dwork, g->dpolar, g->dfallback, g->dwin, g->dunstable, g->dxscratch, g->cbd64, g->dU32, g->dhp, g->dlink, g->dwinmiss, g->dtp64, g->dtp32, g->dxc64, g->dxc32, g->dlinkflags, g->dgap, g->drescue_idx, g->drescue, g->drescue_const, g->sm.d, g->fc.d64, g->fc.d32, g->sp.d, g->lt.d64};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (void* p : g->pinned) (void)hipHostUnregister(p);
@@ -169,10 +172,8 @@ static void gp_free(moihgp_gp* g) {
     if (g->hflag) (void)hipHostFree(g->hflag);
     for (hipEvent_t e : g->prof_ev) (void)hipEventDestroy(e);
     if (g->order_ev) (void)hipEventDestroy(g->order_ev);
-    if (g->sm.ev) (void)hipEventDestroy(g->sm.ev);
-    if (g->fc_ev) (void)hipEventDestroy(g->fc_ev);
-    if (g->sp.ev) (void)hipEventDestroy(g->sp.ev);
-    if (g->lt_ev) (void)hipEventDestroy(g->lt_ev);
+    for (hipEvent_t e : {g->sm.ev, g->fc.ev, g->sp.ev, g->lt.ev})
+        if (e) (void)hipEventDestroy(e);
     if (g->stream) (void)hipStreamDestroy(g->stream);
     delete g;
 }
@@ -227,6 +228,19 @@ static void ensure_tables(moihgp_gp* g, LazyTables& t, size_t block, hipStream_t
     } else if (s != t.built_on) {
         MOIHGP_HIP_FATAL(hipStreamWaitEvent(s, t.ev, 0));
     }
+}
+// CallTables: the buffer(s) of `block` scalars per latent and the event on first use, then the wait for the last call that used them -- only where
+// that call ran on another stream.  The caller builds the tables and launches what reads them on s, then records the end (call_tables_end).
+static void call_tables_begin(moihgp_gp* g, CallTables& t, size_t block, bool with_fp32, hipStream_t s) {
+    if (!t.d64) t.d64 = dev_alloc<double>(g->L * block);
+    if (with_fp32 && !t.d32) t.d32 = dev_alloc<float>(g->L * block);
+    if (!t.ev) MOIHGP_HIP_FATAL(hipEventCreateWithFlags(&t.ev, hipEventDisableTiming));
+    if (t.ev_set && s != t.last) MOIHGP_HIP_FATAL(hipStreamWaitEvent(s, t.ev, 0));
+}
+static void call_tables_end(CallTables& t, hipStream_t s) {
+    t.last = s;
+    t.ev_set = true;
+    MOIHGP_HIP_FATAL(hipEventRecord(t.ev, s));
 }
 // host copy of the blocks of latents [l0, l0 + n) of tables that ensure_tables has just seen to (through the handle's stream)
 static std::vector<double> read_tables(moihgp_gp* g, const LazyTables& t, size_t block, size_t l0, size_t n) {
@@ -773,10 +787,13 @@ int moihgp_get_latent(moihgp_gp* gp, size_t l, double* A, double* K, double* S, 
     return guard_rc([&] { return get_latent_impl(gp, l, A, K, S, HA, AKHA, dA, dS, dK, dAKHA, HdA, iters); });
 }
 
-static int check_handle_dtype(moihgp_gp* gp, int dtype) {
-    if (!gp) { set_last_error("null handle"); return 1; }
+static int check_dtype(int dtype) {
     if (dtype != MOIHGP_F64 && dtype != MOIHGP_F32) { set_last_error("dtype must be MOIHGP_F64 or MOIHGP_F32"); return 1; }
     return 0;
+}
+static int check_handle_dtype(moihgp_gp* gp, int dtype) {
+    if (!gp) { set_last_error("null handle"); return 1; }
+    return check_dtype(dtype);
 }
 
 static int check_stream_args(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld, const void* x) {
@@ -1067,17 +1084,53 @@ static int check_no_overlap(const void* in, size_t in_elems, const void* out, si
     return 0;
 }
 
+
+// The output buffers of a whole-stream smoother, forecast, fixed-lag or sampling call, stated as data: a row buffer [L][ld_out] (K == 0) or K planes
+// of L such rows, plane_stride scalars apart.  name, subject: the entry's words for the buffer in the error texts ("lag buffer", "the lag buffer").
+struct OutBuf {
+    const void* p;
+    const char *name, *subject;
+    size_t K = 0, plane_stride = 0;
+};
+// ... checked in a fixed order, so that a bad call always reports the same first error: every buffer's base and row stride (and its planes), then
+// every buffer against the input stream, then the buffers against each other.  The sweeps read the stream, and the later buffers the earlier ones,
+// beside or behind the ticks they write, so none of them may overlap.  (One ld_out serves all buffers of a call: include/moihgp.h.)
+static int check_outputs(const SweepIo& io, std::initializer_list<OutBuf> outs) {
+    const size_t es = io.dtype == MOIHGP_F64 ? 8 : 4;
+    auto elems = [&](const OutBuf& b) { return (b.K ? (b.K - 1) * b.plane_stride : 0) + io.L * io.ld_out; };
+    char msg[96];
+    for (const OutBuf& b : outs) {
+        if (int rc = check_out_rows(b.p, b.name, io.T, 'T', io.ld_out, es)) return rc;
+        if (b.K)
+            if (int rc = check_planes(b.p, b.plane_stride, io.L, io.ld_out, es)) return rc;
+    }
+    for (const OutBuf& b : outs) {
+        snprintf(msg, sizeof msg, "%s must not overlap the input stream", b.subject);
+        if (int rc = check_no_overlap(io.Ty, io.L * io.ld, b.p, elems(b), io.T, es, msg)) return rc;
+    }
+    for (const OutBuf* a = outs.begin(); a != outs.end(); a++)
+        for (const OutBuf* b = a + 1; b != outs.end(); b++) {
+            snprintf(msg, sizeof msg, "%s must not overlap %s", b->subject, a->name);
+            if (int rc = check_no_overlap(a->p, elems(*a), b->p, elems(*b), io.T, es, msg)) return rc;
+        }
+    return 0;
+}
+
+// The record of such a call (common.h SweepIo): rows is its row-shaped output (ysmooth, ypred) or NULL, ld_out the row stride of all its outputs.
+static SweepIo stream_sweep_io(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x, void* rows, size_t ld_out,
+                               void* stream) {
+    return SweepIo{dtype, Ty, T, ld_in, gp->L, x_in, x, rows, ld_out, nullptr, nullptr, (hipStream_t)stream};
+}
+
 static int smooth_stream_impl(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x, void* ys, size_t ld_out,
                               int* status, void* stream) {
     if (int rc = check_sweep_call(gp, dtype, Ty, T, ld_in, x_in, x)) return rc;
-    const size_t es = dtype == MOIHGP_F64 ? 8 : 4;
-    if (int rc = check_out_rows(ys, "ysmooth", T, 'T', ld_out, es)) return rc;
+    const SweepIo io = stream_sweep_io(gp, dtype, Ty, T, ld_in, x_in, x, ys, ld_out, stream);
     // the backward sweep reads y after the forward one wrote the predicted means: the two may not overlap
-    if (int rc = check_no_overlap(Ty, gp->L * ld_in, ys, gp->L * ld_out, T, es, "ysmooth must not overlap the input stream")) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if (int rc = ensure_smoother(gp, s)) return rc;
-    note_user_stream(gp, s);
-    launch_smooth_stream(gp->d, dtype, Ty, T, ld_in, gp->L, gp->sm.d, x_in, x, ys, ld_out, status, gp->opt_smoother_path, s);
+    if (int rc = check_outputs(io, {{ys, "ysmooth", "ysmooth"}})) return rc;
+    if (int rc = ensure_smoother(gp, io.stream)) return rc;
+    note_user_stream(gp, io.stream);
+    launch_smooth_stream(gp->d, io, gp->sm.d, status, gp->opt_smoother_path);
     return 0;
 }
 
@@ -1127,56 +1180,60 @@ int moihgp_latent_variances(moihgp_gp* gp, double* var_filtered, double* var_smo
 }
 
 // ---- multi-horizon forecasts (forecast.hip) -----------------------------------------------------------------------------------------------------
-// The tables depend on the call's horizons and gains, so every call builds them on its own stream into the handle's two buffers.
-static void forecast_begin(moihgp_gp* g, hipStream_t s) {
-    if (!g->dfc64) { g->dfc64 = dev_alloc<double>(g->L * (size_t)fc_size(g->d)); g->dfc32 = dev_alloc<float>(g->L * (size_t)fc_size(g->d)); }
-    if (!g->fc_ev) MOIHGP_HIP_FATAL(hipEventCreateWithFlags(&g->fc_ev, hipEventDisableTiming));
-    if (g->fc_ev_set && s != g->fc_last) MOIHGP_HIP_FATAL(hipStreamWaitEvent(s, g->fc_ev, 0));
-}
-static void forecast_end(moihgp_gp* g, hipStream_t s) {
-    g->fc_last = s;
-    g->fc_ev_set = true;
-    MOIHGP_HIP_FATAL(hipEventRecord(g->fc_ev, s));
-}
-
-static int check_horizons(const int* horizons, size_t K, FcHorizons& hz) {
-    if (K < 1 || K > (size_t)MOIHGP_FORECAST_MAX_HORIZONS) { set_last_error("forecast: the number of horizons (%zu) must be 1 .. %d", K, MOIHGP_FORECAST_MAX_HORIZONS); return 1; }
-    if (!horizons) { set_last_error("forecast: null horizons"); return 1; }
-    for (size_t k = 0; k < (size_t)kFcMaxHorizons; k++) hz.h[k] = 0;
+// One validator for the lists of both: 1 .. most entries in 0 .. 2^20 into list[8], zero padded; entry, noun: the error texts' words ("forecast", "horizon").
+static int check_int_list(const char* entry, const char* noun, const int* in, size_t K, int most, int (&list)[8]) {
+    if (K < 1 || K > (size_t)most) { set_last_error("%s: the number of %ss (%zu) must be 1 .. %d", entry, noun, K, most); return 1; }
+    if (!in) { set_last_error("%s: null %ss", entry, noun); return 1; }
+    for (int& v : list) v = 0;
     for (size_t k = 0; k < K; k++) {
-        if (horizons[k] < 0 || horizons[k] > (1 << 20)) { set_last_error("forecast: horizon %zu (%d) must be 0 .. 2^20", k, horizons[k]); return 1; }
-        hz.h[k] = horizons[k];
+        if (in[k] < 0 || in[k] > (1 << 20)) { set_last_error("%s: %s %zu (%d) must be 0 .. 2^20", entry, noun, k, in[k]); return 1; }
+        list[k] = in[k];
     }
     return 0;
+}
+
+// The variances of both, [K][L] into var: build() has begun t and launched its tables of `block` doubles per latent on the handle's stream; column
+// var_off + k of every latent's block holds the variance of list entry k.  (Nothing to read without var: the call then only validates.)
+static int read_call_variances(moihgp_gp* gp, CallTables& t, size_t block, size_t var_off, size_t K, double* var, const std::function<void()>& build) {
+    if (int rc = ensure_smoother(gp, gp->stream)) return rc;
+    if (!var) return 0;
+    build();
+    std::vector<double> b(gp->L * block);
+    MOIHGP_HIP_FATAL(hipMemcpyAsync(b.data(), t.d64, sizeof(double) * b.size(), hipMemcpyDeviceToHost, gp->stream));
+    call_tables_end(t, gp->stream);
+    MOIHGP_HIP_FATAL(hipStreamSynchronize(gp->stream));
+    for (size_t k = 0; k < K; k++)
+        for (size_t l = 0; l < gp->L; l++) var[k * gp->L + l] = b[l * block + var_off + k];
+    return 0;
+}
+
+// The tables depend on the call's horizons and gains, so every call builds them on its own stream into the handle's two buffers.
+static void build_forecast_tables(moihgp_gp* gp, const FcHorizons& hz, size_t K, int gains, hipStream_t s) {
+    call_tables_begin(gp, gp->fc, (size_t)fc_size(gp->d), true, s);
+    launch_forecast_tables(kernel_base(gp->kernel), gp->d, gp->cb64, gp->sm.d, gp->L, hz, (int)K, gains, gp->fc.d64, gp->fc.d32, s);
 }
 
 static int forecast_stream_impl(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x, const int* horizons, size_t K,
                                 void* fc, size_t ld_out, size_t plane_stride, int gains, int* status, void* stream) {
     if (int rc = check_sweep_call(gp, dtype, Ty, T, ld_in, x_in, x)) return rc;
     FcHorizons hz;
-    if (int rc = check_horizons(horizons, K, hz)) return rc;
+    if (int rc = check_int_list("forecast", "horizon", horizons, K, MOIHGP_FORECAST_MAX_HORIZONS, hz.h)) return rc;
     if (gains != MOIHGP_GAINS_KALMAN && gains != MOIHGP_GAINS_HANDLE) { set_last_error("forecast: gains must be MOIHGP_GAINS_KALMAN (0) or MOIHGP_GAINS_HANDLE (1)"); return 1; }
-    const size_t es = dtype == MOIHGP_F64 ? 8 : 4;
-    if (int rc = check_out_rows(fc, "forecast buffer", T, 'T', ld_out, es)) return rc;
-    if (int rc = check_planes(fc, plane_stride, gp->L, ld_out, es)) return rc;
+    const SweepIo io = stream_sweep_io(gp, dtype, Ty, T, ld_in, x_in, x, nullptr, ld_out, stream);
     // a segment of y is read after earlier segments' planes were written: the two may not overlap
-    if (int rc = check_no_overlap(Ty, gp->L * ld_in, fc, (K - 1) * plane_stride + gp->L * ld_out, T, es, "the forecast buffer must not overlap the input stream")) return rc;
+    if (int rc = check_outputs(io, {{fc, "forecast buffer", "the forecast buffer", K, plane_stride}})) return rc;
     if (kernel_stack(gp->kernel)) { set_last_error("forecast: stacked models are not supported (Matern-3/2 and -5/2 only)"); return 3; }
-    hipStream_t s = (hipStream_t)stream;
     if (gains == MOIHGP_GAINS_KALMAN)
-        if (int rc = ensure_smoother(gp, s)) return rc;
-    note_user_stream(gp, s);
-    forecast_begin(gp, s);
-    launch_forecast_tables(kernel_base(gp->kernel), gp->d, gp->cb64, gp->sm.d, gp->L, hz, (int)K, gains, gp->dfc64, gp->dfc32, s);
-    launch_forecast_stream(gp->d, dtype, Ty, T, ld_in, gp->L, gp->dfc64, gp->dfc32, x_in, x, fc, ld_out, plane_stride, (int)K, status,
-                           gp->opt_forecast_path, s);
-    forecast_end(gp, s);
+        if (int rc = ensure_smoother(gp, io.stream)) return rc;
+    note_user_stream(gp, io.stream);
+    build_forecast_tables(gp, hz, K, gains, io.stream);
+    launch_forecast_stream(gp->d, io, gp->fc.d64, gp->fc.d32, SweepPlanes{fc, plane_stride, (int)K}, status, gp->opt_forecast_path);
+    call_tables_end(gp->fc, io.stream);
     return 0;
 }
 
 static int forecast_tail_impl(moihgp_gp* gp, int dtype, const void* x, size_t n, void* tail, size_t ld_out, void* stream) {
-    if (!gp) { set_last_error("null handle"); return 1; }
-    if (dtype != MOIHGP_F64 && dtype != MOIHGP_F32) { set_last_error("dtype must be MOIHGP_F64 or MOIHGP_F32"); return 1; }
+    if (int rc = check_handle_dtype(gp, dtype)) return rc;
     if (!x || (n > 0 && !tail)) { set_last_error("forecast_tail: null state/tail pointer"); return 1; }
     if (n > ((size_t)1 << 20)) { set_last_error("forecast_tail: n (%zu) must be <= 2^20", n); return 1; }
     if (int rc = check_out_rows(tail, "tail", n, 'n', ld_out, dtype == MOIHGP_F64 ? 8 : 4, true)) return rc;
@@ -1190,19 +1247,9 @@ static int forecast_tail_impl(moihgp_gp* gp, int dtype, const void* x, size_t n,
 static int forecast_variances_impl(moihgp_gp* gp, const int* horizons, size_t K, double* var) {
     if (!gp) { set_last_error("null handle"); return 1; }
     FcHorizons hz;
-    if (int rc = check_horizons(horizons, K, hz)) return rc;
-    if (int rc = ensure_smoother(gp, gp->stream)) return rc;
-    if (!var) return 0;
-    forecast_begin(gp, gp->stream);
-    launch_forecast_tables(kernel_base(gp->kernel), gp->d, gp->cb64, gp->sm.d, gp->L, hz, (int)K, MOIHGP_GAINS_KALMAN, gp->dfc64, gp->dfc32, gp->stream);
-    const size_t bs = (size_t)fc_size(gp->d), vo = (size_t)(gp->d == 2 ? FT<2>::VAR : FT<3>::VAR);
-    std::vector<double> b(gp->L * bs);
-    MOIHGP_HIP_FATAL(hipMemcpyAsync(b.data(), gp->dfc64, sizeof(double) * b.size(), hipMemcpyDeviceToHost, gp->stream));
-    forecast_end(gp, gp->stream);
-    MOIHGP_HIP_FATAL(hipStreamSynchronize(gp->stream));
-    for (size_t k = 0; k < K; k++)
-        for (size_t l = 0; l < gp->L; l++) var[k * gp->L + l] = b[l * bs + vo + k];
-    return 0;
+    if (int rc = check_int_list("forecast", "horizon", horizons, K, MOIHGP_FORECAST_MAX_HORIZONS, hz.h)) return rc;
+    return read_call_variances(gp, gp->fc, (size_t)fc_size(gp->d), (size_t)(gp->d == 2 ? FT<2>::VAR : FT<3>::VAR), K, var,
+                               [&] { build_forecast_tables(gp, hz, K, MOIHGP_GAINS_KALMAN, gp->stream); });
 }
 
 int moihgp_forecast_stream(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x, const int* horizons, size_t K,
@@ -1218,70 +1265,34 @@ int moihgp_forecast_variances(moihgp_gp* gp, const int* horizons, size_t K, doub
 
 // ---- fixed-lag smoothing (lagged.hip) ------------------------------------------------------------------------------------------------------------
 // The tables depend on the call's lags, so every call builds them on its own stream into the handle's buffer, as the forecasts do.
-static void lagged_begin(moihgp_gp* g, hipStream_t s) {
-    if (!g->dlt) g->dlt = dev_alloc<double>(g->L * (size_t)lt_size(g->d));
-    if (!g->lt_ev) MOIHGP_HIP_FATAL(hipEventCreateWithFlags(&g->lt_ev, hipEventDisableTiming));
-    if (g->lt_ev_set && s != g->lt_last) MOIHGP_HIP_FATAL(hipStreamWaitEvent(s, g->lt_ev, 0));
-}
-static void lagged_end(moihgp_gp* g, hipStream_t s) {
-    g->lt_last = s;
-    g->lt_ev_set = true;
-    MOIHGP_HIP_FATAL(hipEventRecord(g->lt_ev, s));
-}
-
-static int check_lags(const int* lags, size_t K, LagList& ll) {
-    if (K < 1 || K > (size_t)MOIHGP_LAGGED_MAX_LAGS) { set_last_error("lagged: the number of lags (%zu) must be 1 .. %d", K, MOIHGP_LAGGED_MAX_LAGS); return 1; }
-    if (!lags) { set_last_error("lagged: null lags"); return 1; }
-    for (size_t k = 0; k < (size_t)kLagMaxLags; k++) ll.lag[k] = 0;
-    for (size_t k = 0; k < K; k++) {
-        if (lags[k] < 0 || lags[k] > (1 << 20)) { set_last_error("lagged: lag %zu (%d) must be 0 .. 2^20", k, lags[k]); return 1; }
-        ll.lag[k] = lags[k];
-    }
-    return 0;
+static void build_lagged_tables(moihgp_gp* gp, const LagList& ll, size_t K, hipStream_t s) {
+    call_tables_begin(gp, gp->lt, (size_t)lt_size(gp->d), false, s);
+    launch_lagged_tables(gp->d, gp->sm.d, gp->L, ll, (int)K, gp->lt.d64, s);
 }
 
 static int lagged_stream_impl(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x, size_t T_state, const int* lags,
                               size_t K, void* ypred, void* out, size_t ld_out, size_t plane_stride, int* status, void* stream) {
     if (int rc = check_sweep_call(gp, dtype, Ty, T, ld_in, x_in, x)) return rc;
     LagList ll;
-    if (int rc = check_lags(lags, K, ll)) return rc;
+    if (int rc = check_int_list("lagged", "lag", lags, K, MOIHGP_LAGGED_MAX_LAGS, ll.lag)) return rc;
     if (T_state > T) { set_last_error("lagged: T_state (%zu) must be <= T (%zu)", T_state, T); return 1; }
-    const size_t es = dtype == MOIHGP_F64 ? 8 : 4;
-    if (int rc = check_out_rows(ypred, "ypred", T, 'T', ld_out, es)) return rc;
-    if (int rc = check_out_rows(out, "lag buffer", T, 'T', ld_out, es)) return rc;
-    if (int rc = check_planes(out, plane_stride, gp->L, ld_out, es)) return rc;
+    const SweepIo io = stream_sweep_io(gp, dtype, Ty, T, ld_in, x_in, x, ypred, ld_out, stream);
     // the backward sweep reads y and the predicted means to the right of the ticks it writes: the three may not overlap
-    const size_t out_elems = (K - 1) * plane_stride + gp->L * ld_out;
-    if (int rc = check_no_overlap(Ty, gp->L * ld_in, ypred, gp->L * ld_out, T, es, "ypred must not overlap the input stream")) return rc;
-    if (int rc = check_no_overlap(Ty, gp->L * ld_in, out, out_elems, T, es, "the lag buffer must not overlap the input stream")) return rc;
-    if (int rc = check_no_overlap(ypred, gp->L * ld_out, out, out_elems, T, es, "the lag buffer must not overlap ypred")) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if (int rc = ensure_smoother(gp, s)) return rc;
-    note_user_stream(gp, s);
-    lagged_begin(gp, s);
-    launch_lagged_tables(gp->d, gp->sm.d, gp->L, ll, (int)K, gp->dlt, s);
-    launch_lagged_stream(gp->d, dtype, Ty, T, ld_in, gp->L, gp->sm.d, gp->dlt, x_in, x, T_state, ll, (int)K, ypred, out, ld_out, plane_stride, status,
-                         gp->opt_lagged_path, s);
-    lagged_end(gp, s);
+    if (int rc = check_outputs(io, {{ypred, "ypred", "ypred"}, {out, "lag buffer", "the lag buffer", K, plane_stride}})) return rc;
+    if (int rc = ensure_smoother(gp, io.stream)) return rc;
+    note_user_stream(gp, io.stream);
+    build_lagged_tables(gp, ll, K, io.stream);
+    launch_lagged_stream(gp->d, io, gp->sm.d, gp->lt.d64, T_state, ll, SweepPlanes{out, plane_stride, (int)K}, status, gp->opt_lagged_path);
+    call_tables_end(gp->lt, io.stream);
     return 0;
 }
 
 static int lagged_variances_impl(moihgp_gp* gp, const int* lags, size_t K, double* var) {
     if (!gp) { set_last_error("null handle"); return 1; }
     LagList ll;
-    if (int rc = check_lags(lags, K, ll)) return rc;
-    if (int rc = ensure_smoother(gp, gp->stream)) return rc;
-    if (!var) return 0;
-    lagged_begin(gp, gp->stream);
-    launch_lagged_tables(gp->d, gp->sm.d, gp->L, ll, (int)K, gp->dlt, gp->stream);
-    const size_t bs = (size_t)lt_size(gp->d), vo = (size_t)(gp->d == 2 ? LT<2>::VAR : LT<3>::VAR);
-    std::vector<double> b(gp->L * bs);
-    MOIHGP_HIP_FATAL(hipMemcpyAsync(b.data(), gp->dlt, sizeof(double) * b.size(), hipMemcpyDeviceToHost, gp->stream));
-    lagged_end(gp, gp->stream);
-    MOIHGP_HIP_FATAL(hipStreamSynchronize(gp->stream));
-    for (size_t k = 0; k < K; k++)
-        for (size_t l = 0; l < gp->L; l++) var[k * gp->L + l] = b[l * bs + vo + k];
-    return 0;
+    if (int rc = check_int_list("lagged", "lag", lags, K, MOIHGP_LAGGED_MAX_LAGS, ll.lag)) return rc;
+    return read_call_variances(gp, gp->lt, (size_t)lt_size(gp->d), (size_t)(gp->d == 2 ? LT<2>::VAR : LT<3>::VAR), K, var,
+                               [&] { build_lagged_tables(gp, ll, K, gp->stream); });
 }
 
 int moihgp_lagged_stream(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x, size_t T_state, const int* lags,
@@ -1305,20 +1316,13 @@ static int sample_stream_impl(moihgp_gp* gp, int dtype, const void* Ty, size_t T
                               int* status, void* stream) {
     if (int rc = check_sweep_call(gp, dtype, Ty, T, ld_in, x_in, x)) return rc;
     if (nsamples < 1 || nsamples > 65535) { set_last_error("sample: nsamples (%zu) must be 1 .. 65535", nsamples); return 1; }
-    const size_t es = dtype == MOIHGP_F64 ? 8 : 4;
-    if (int rc = check_out_rows(ys, "ysmooth", T, 'T', ld_out, es)) return rc;
-    if (int rc = check_out_rows(samples, "sample buffer", T, 'T', ld_out, es)) return rc;
-    if (int rc = check_planes(samples, plane_stride, gp->L, ld_out, es)) return rc;
-    const size_t sample_elems = (nsamples - 1) * plane_stride + gp->L * ld_out;
-    if (int rc = check_no_overlap(Ty, gp->L * ld_in, ys, gp->L * ld_out, T, es, "ysmooth must not overlap the input stream")) return rc;
-    if (int rc = check_no_overlap(Ty, gp->L * ld_in, samples, sample_elems, T, es, "the sample buffer must not overlap the input stream")) return rc;
-    if (int rc = check_no_overlap(ys, gp->L * ld_out, samples, sample_elems, T, es, "the sample buffer must not overlap ysmooth")) return rc;
-    hipStream_t s = (hipStream_t)stream;
-    if (int rc = ensure_sampler(gp, s)) return rc;
-    note_user_stream(gp, s);
-    launch_smooth_stream(gp->d, dtype, Ty, T, ld_in, gp->L, gp->sm.d, x_in, x, ys, ld_out, nullptr, gp->opt_smoother_path, s);
-    launch_sample_stream(gp->d, dtype, T, gp->L, gp->sm.d, gp->sp.d, ys, ld_out, samples, plane_stride, (int)nsamples, seed, sample0, latent0, status,
-                         gp->opt_sample_path, s);
+    const SweepIo io = stream_sweep_io(gp, dtype, Ty, T, ld_in, x_in, x, ys, ld_out, stream);
+    if (int rc = check_outputs(io, {{ys, "ysmooth", "ysmooth"}, {samples, "sample buffer", "the sample buffer", nsamples, plane_stride}})) return rc;
+    if (int rc = ensure_sampler(gp, io.stream)) return rc;
+    note_user_stream(gp, io.stream);
+    launch_smooth_stream(gp->d, io, gp->sm.d, nullptr, gp->opt_smoother_path);
+    launch_sample_stream(gp->d, io, gp->sm.d, gp->sp.d, SweepPlanes{samples, plane_stride, (int)nsamples}, seed, sample0, latent0, status,
+                         gp->opt_sample_path);
     return 0;
 }
 
@@ -1361,7 +1365,7 @@ int moihgp_get_sampler(moihgp_gp* gp, size_t l, double* B, double* sigma2, doubl
 
 int moihgp_stream_retile(int dtype, const void* src, void* dst, size_t L, size_t T, size_t ld, int to_tiled, void* stream) {
     return guard_rc([&] {
-        if (dtype != MOIHGP_F64 && dtype != MOIHGP_F32) { set_last_error("dtype must be MOIHGP_F64 or MOIHGP_F32"); return 1; }
+        if (int rc = check_dtype(dtype)) return rc;
         if (!src || !dst) { set_last_error("null stream pointer"); return 1; }
         return launch_stream_retile(dtype, src, dst, L, T, ld, to_tiled, (hipStream_t)stream);
     });
@@ -1685,8 +1689,8 @@ int moihgp_release_stream(moihgp_gp* gp, void* stream) {
             MOIHGP_HIP_FATAL(hipEventRecord(gp->order_ev, s));
             MOIHGP_HIP_FATAL(hipStreamWaitEvent(gp->stream, gp->order_ev, 0));
             gp->user_streams.erase(gp->user_streams.begin() + (long)i);
-            if (gp->fc_last == s) gp->fc_last = gp->stream;   // (the handle's stream now follows s: a later forecast on any other stream waits for fc_ev)
-            if (gp->lt_last == s) gp->lt_last = gp->stream;   // (the same for the fixed-lag tables and lt_ev)
+            for (CallTables* t : {&gp->fc, &gp->lt})          // (the handle's stream now follows s: a later forecast or fixed-lag call on any other
+                if (t->last == s) t->last = gp->stream;       // stream waits for the tables' event)
             break;
         }
         return 0;

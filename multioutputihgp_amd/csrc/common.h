@@ -135,15 +135,18 @@ void launch_rescue_scatter(const int* idx, size_t n, const double* rows, size_t 
                            float* yhat, size_t ldo, float* x, double* nll, hipStream_t s);
 // stationary_x.hip: the reference's own models (d = 2, 3) in the stacked layout, for the few-latents team kernel: [n][xc_size(d)] from the CB blocks
 void launch_xc_from_cb(int d, const double* cb64, size_t n, double* xc64, float* xc32, hipStream_t stream);
-// ---- filter sweeps: what every launcher of one is handed ----
+// ---- sweeps over whole streams: what every launcher of one is handed ----
 // The stream of one call, where its results go, and the queue it runs on.  Filled once per call (capi.cpp); the launchers unpack it at the
-// kernel launch line -- a kernel never sees the record.
+// kernel launch line -- a kernel never sees the record.  The filter sweeps take it as it stands; the smoother, forecast, fixed-lag and sampling
+// sweeps leave nll, total and the profile events NULL and take beside it what only they need (tables, SweepPlanes, status, path, their scalars).
 struct SweepIo {
     int dtype;                          // 0 = fp64, 1 = fp32 (MOIHGP_F64 / MOIHGP_F32): the scalar type behind the void pointers
     const void* Ty; size_t T, ld, L;    // [L][ld] series-major, T ticks per row (segment-major streams: ld unused, 0)
     const void* xin; void* x;           // [L][d] start state / end state (may alias)
-    void* yhat = nullptr;               // [L][ld_out] filtered means, or NULL
-    size_t ld_out = 0;                  // row stride of yhat: always set where yhat is (sweep_io() fills in ld when the caller leaves it 0)
+    void* yhat = nullptr;               // [L][ld_out] the call's row-shaped output, or NULL: filtered means (filter sweeps), ysmooth (smoother, sampler:
+                                        // which reads it), ypred (fixed-lag smoother)
+    size_t ld_out = 0;                  // row stride of yhat: always set where yhat is (sweep_io() fills in ld when the caller leaves it 0), and
+                                        // of the rows of a sweep's SweepPlanes
     double* nll = nullptr;              // [L] or NULL
     double* total = nullptr;            // device scalar: sum of nll[], or NULL
     hipStream_t stream = nullptr;
@@ -230,39 +233,43 @@ int launch_filter_stream_tiled(int d, const SweepIo& io, const double* cb64, con
 // smoother.hip: steady-state RTS smoothing (include/moihgp.h moihgp_smooth_stream).  Per-latent fp64 block SM<D> of sm_size(d) doubles
 // (stream_tables.h, which names its fields).
 void launch_smoother_tables(int kernel, int d, const double* cb64, size_t L, double* tabs, hipStream_t stream);
-// path: -1 automatic (scan kernels for the latents that pass the growth bound), 0 scan kernels, 1 serial fp64 for every latent
-void launch_smooth_stream(int d, int dtype, const void* Ty, size_t T, size_t ld_in, size_t L, const double* tabs, const void* x_in, void* x,
-                          void* ys, size_t ld_out, int* status, int path, hipStream_t stream);
-// the smoother's forward sweep alone, for the fixed-lag smoother: predicted means into p [L][ld_out], and into x the filtered state after tick
-// T_state - 1 (T_state <= T; 0: x_in), for the latents the scan kernels take (and the NaN row and state of a failed one)
-void launch_smooth_forward(int d, int dtype, const void* Ty, size_t T, size_t ld_in, size_t L, const double* tabs, const void* x_in, void* x,
-                           size_t T_state, void* p, size_t ld_out, int path, hipStream_t stream);
+// The K planes [L][io.ld_out] a forecast, fixed-lag or sampling sweep writes beside its SweepIo: one per horizon, lag or sample.
+struct SweepPlanes {
+    void* base;
+    size_t stride;                      // scalars from one plane to the next
+    int K;
+};
+// io.yhat: the smoothed means ysmooth.  path: -1 automatic (scan kernels for the latents that pass the growth bound), 0 scan kernels, 1 serial fp64
+// for every latent
+void launch_smooth_stream(int d, const SweepIo& io, const double* tabs, int* status, int path);
+// the smoother's forward sweep alone, for the fixed-lag smoother: predicted means into io.yhat, and into io.x the filtered state after tick
+// T_state - 1 (T_state <= T; 0: io.xin), for the latents the scan kernels take (and the NaN row and state of a failed one)
+void launch_smooth_forward(int d, const SweepIo& io, const double* tabs, size_t T_state, int path);
 // forecast.hip: multi-horizon forecasts (include/moihgp.h moihgp_forecast_stream).  Per-latent block FT<D> of fc_size(d) scalars (stream_tables.h), built
 // per call for the call's horizons, as an fp64 and an fp32 copy; sm: the smoother's blocks (gains 0: Kalman-form K, A - K H A, PF) or unused (gains 1: the handle's).
 constexpr int kFcMaxHorizons = 8;   // MOIHGP_FORECAST_MAX_HORIZONS
 struct FcHorizons { int h[kFcMaxHorizons]; };
 void launch_forecast_tables(int kernel, int d, const double* cb64, const double* sm, size_t L, const FcHorizons& hz, int K, int gains, double* t64,
                             float* t32, hipStream_t stream);
-// path: -1 automatic (the scan for the latents that pass the growth bound), 0 scan for every latent, 1 serial fp64 for every latent
-void launch_forecast_stream(int d, int dtype, const void* Ty, size_t T, size_t ld_in, size_t L, const double* t64, const float* t32, const void* x_in,
-                            void* x, void* fc, size_t ld_out, size_t plane_stride, int K, int* status, int path, hipStream_t stream);
+// io.yhat: unused (NULL).  path: -1 automatic (the scan for the latents that pass the growth bound), 0 scan for every latent, 1 serial fp64 for
+// every latent
+void launch_forecast_stream(int d, const SweepIo& io, const double* t64, const float* t32, const SweepPlanes& fc, int* status, int path);
 void launch_forecast_tail(int d, int dtype, const double* cb64, size_t L, const void* x, size_t n, void* tail, size_t ld_out, hipStream_t stream);
 // lagged.hip: fixed-lag smoothing (include/moihgp.h moihgp_lagged_stream).  Per-latent fp64 block LT<D> of lt_size(d) doubles (stream_tables.h), built per
-// call for the call's lags from the smoother's blocks sm, which the sweeps read beside it.  ypred [L][ld_out] receives the forward pass's predicted
-// means, out the K planes; x the filtered state after tick T_state - 1.  path as launch_smooth_stream's.
+// call for the call's lags from the smoother's blocks sm, which the sweeps read beside it.  io.yhat (ypred) receives the forward pass's predicted
+// means, out the K planes; io.x the filtered state after tick T_state - 1.  path as launch_smooth_stream's.
 constexpr int kLagMaxLags = 8;   // MOIHGP_LAGGED_MAX_LAGS
 struct LagList { int lag[kLagMaxLags]; };
 void launch_lagged_tables(int d, const double* sm, size_t L, const LagList& lags, int K, double* lt, hipStream_t stream);
-void launch_lagged_stream(int d, int dtype, const void* Ty, size_t T, size_t ld_in, size_t L, const double* sm, const double* lt, const void* x_in,
-                          void* x, size_t T_state, const LagList& lags, int K, void* ypred, void* out, size_t ld_out, size_t plane_stride, int* status,
-                          int path, hipStream_t stream);
+void launch_lagged_stream(int d, const SweepIo& io, const double* sm, const double* lt, size_t T_state, const LagList& lags, const SweepPlanes& out,
+                          int* status, int path);
 // sampler.hip: seeded steady-state posterior samples (include/moihgp.h moihgp_sample_stream).  Per-latent fp64 block SP<D> of sp_size(d) doubles
-// (stream_tables.h) from the smoother's blocks sm; ysm: the smoothed means [L][ld_out] the deviations are added to; samples [S][L][ld_out], planes
-// plane_stride apart.  path as launch_smooth_stream's.  status: 0 ok, 1 Kalman DARE failed, 2 realization failed (sample rows NaN).
+// (stream_tables.h) from the smoother's blocks sm; io.yhat: the smoothed means the deviations are added to (read; of io, only it, T, L, ld_out and the
+// queue matter here); samples: one plane per sample.  path as launch_smooth_stream's.  status: 0 ok, 1 Kalman DARE failed, 2 realization failed
+// (sample rows NaN).
 void launch_sampler_tables(int d, const double* sm, size_t L, double* sp, hipStream_t stream);
-void launch_sample_stream(int d, int dtype, size_t T, size_t L, const double* sm, const double* sp, const void* ysm, size_t ld_out, void* samples,
-                          size_t plane_stride, int nsamples, unsigned long long seed, unsigned sample0, unsigned latent0, int* status, int path,
-                          hipStream_t stream);
+void launch_sample_stream(int d, const SweepIo& io, const double* sm, const double* sp, const SweepPlanes& samples, unsigned long long seed,
+                          unsigned sample0, unsigned latent0, int* status, int path);
 void launch_sample_noise(unsigned long long seed, unsigned latent0, size_t L, unsigned sample0, size_t S, size_t T, float* noise, size_t ld, float* start,
                          hipStream_t stream);
 // series-major [L][ld] <-> segment-major [ceil(T / SEG)][L][SEG] (to_tiled != 0: src is series-major; ticks past T are written as zeros)

@@ -300,37 +300,32 @@ void launch_forecast_tables(int kernel, int d, const double* cb64, const double*
     MOIHGP_HIP_FATAL(hipGetLastError());
 }
 
+// The call's record and its planes are unpacked here, at the launch lines.
 template <typename Tv, int D, int KG>
-static void launch_sweep_kg(const Tv* Ty, size_t T, size_t ld_in, size_t L, const Tv* tabs, const double* t64, const Tv* x_in, Tv* x, Tv* fc,
-                            size_t ld_out, size_t plane_stride, int K, int path, hipStream_t stream) {
+static void launch_sweep_kg(const SweepIo& io, const Tv* tabs, const double* t64, const SweepPlanes& fc, int path) {
     const size_t lds = sizeof(Tv) * (size_t)(1 + KG) * kScanPlane;
-    hipLaunchKernelGGL((forecast_sweep_kernel<Tv, Tv, D, KG>), dim3((unsigned)L), dim3(64), lds, stream, Ty, T, ld_in, tabs, t64, x_in, x, fc, ld_out,
-                       plane_stride, K, path);
+    hipLaunchKernelGGL((forecast_sweep_kernel<Tv, Tv, D, KG>), dim3((unsigned)io.L), dim3(64), lds, io.stream, (const Tv*)io.Ty, io.T, io.ld, tabs, t64,
+                       (const Tv*)io.xin, (Tv*)io.x, (Tv*)fc.base, io.ld_out, fc.stride, fc.K, path);
     MOIHGP_HIP_FATAL(hipGetLastError());
 }
 
 template <typename Tv, int D>
-static void launch_forecast_t(const Tv* Ty, size_t T, size_t ld_in, size_t L, const double* t64, const float* t32, const Tv* x_in, Tv* x, Tv* fc,
-                              size_t ld_out, size_t plane_stride, int K, int* status, int path, hipStream_t stream) {
+static void launch_forecast_t(const SweepIo& io, const double* t64, const float* t32, const SweepPlanes& fc, int* status, int path) {
     const Tv* tabs;
     if constexpr (sizeof(Tv) == 8) tabs = t64; else tabs = t32;
-    if (T > 0 && path != 1) {
+    if (io.T > 0 && path != 1) {
         // horizons staged per replay: one for a single horizon, else two (three LDS planes per wavefront: 13 KB at fp32, 26 KB at fp64)
-        if (K == 1) launch_sweep_kg<Tv, D, 1>(Ty, T, ld_in, L, tabs, t64, x_in, x, fc, ld_out, plane_stride, K, path, stream);
-        else launch_sweep_kg<Tv, D, 2>(Ty, T, ld_in, L, tabs, t64, x_in, x, fc, ld_out, plane_stride, K, path, stream);
+        if (fc.K == 1) launch_sweep_kg<Tv, D, 1>(io, tabs, t64, fc, path);
+        else launch_sweep_kg<Tv, D, 2>(io, tabs, t64, fc, path);
     }
-    hipLaunchKernelGGL((forecast_serial_kernel<Tv, D>), dim3((unsigned)((L + 63) / 64)), dim3(64), 0, stream, Ty, T, ld_in, t64, L, x_in, x, fc, ld_out,
-                       plane_stride, K, status, T > 0 ? path : 1, scan_growth_bound<Tv>());
+    hipLaunchKernelGGL((forecast_serial_kernel<Tv, D>), dim3((unsigned)((io.L + 63) / 64)), dim3(64), 0, io.stream, (const Tv*)io.Ty, io.T, io.ld, t64, io.L,
+                       (const Tv*)io.xin, (Tv*)io.x, (Tv*)fc.base, io.ld_out, fc.stride, fc.K, status, io.T > 0 ? path : 1, scan_growth_bound<Tv>());
     MOIHGP_HIP_FATAL(hipGetLastError());
 }
 
-void launch_forecast_stream(int d, int dtype, const void* Ty, size_t T, size_t ld_in, size_t L, const double* t64, const float* t32, const void* x_in,
-                            void* x, void* fc, size_t ld_out, size_t plane_stride, int K, int* status, int path, hipStream_t stream) {
-    if (L == 0) return;
-    dispatch_stream(d, dtype, [&](auto tv, auto dim) {
-        using Tv = decltype(tv);
-        launch_forecast_t<Tv, decltype(dim)::value>((const Tv*)Ty, T, ld_in, L, t64, t32, (const Tv*)x_in, (Tv*)x, (Tv*)fc, ld_out, plane_stride, K, status, path, stream);
-    });
+void launch_forecast_stream(int d, const SweepIo& io, const double* t64, const float* t32, const SweepPlanes& fc, int* status, int path) {
+    if (io.L == 0) return;
+    dispatch_stream(d, io.dtype, [&](auto tv, auto dim) { launch_forecast_t<decltype(tv), decltype(dim)::value>(io, t64, t32, fc, status, path); });
 }
 
 void launch_forecast_tail(int d, int dtype, const double* cb64, size_t L, const void* x, size_t n, void* tail, size_t ld_out, hipStream_t stream) {

@@ -333,30 +333,30 @@ void launch_lagged_tables(int d, const double* sm, size_t L, const LagList& lags
     MOIHGP_HIP_FATAL(hipGetLastError());
 }
 
+// The call's record and its planes are unpacked here, at the launch lines.
 template <typename Tv, int D, int KG>
-static void launch_bwd_kg(const Tv* Ty, size_t T, size_t ld_in, size_t L, const double* sm, const double* lt, const LagList& lags, int K, const Tv* ypred,
-                          Tv* out, size_t ld_out, size_t plane_stride, Tv* x, int path, hipStream_t stream) {
+static void launch_bwd_kg(const SweepIo& io, const double* sm, const double* lt, const LagList& lags, const SweepPlanes& out, int path) {
     const size_t lds = sizeof(Tv) * (size_t)(2 + KG) * kScanPlane;
-    hipLaunchKernelGGL((lagged_bwd_kernel<Tv, D, KG>), dim3((unsigned)L), dim3(64), lds, stream, Ty, T, ld_in, sm, lt, lags, K, ypred, out, ld_out,
-                       plane_stride, x, path);
+    hipLaunchKernelGGL((lagged_bwd_kernel<Tv, D, KG>), dim3((unsigned)io.L), dim3(64), lds, io.stream, (const Tv*)io.Ty, io.T, io.ld, sm, lt, lags, out.K,
+                       (const Tv*)io.yhat, (Tv*)out.base, io.ld_out, out.stride, (Tv*)io.x, path);
     MOIHGP_HIP_FATAL(hipGetLastError());
 }
 
-void launch_lagged_stream(int d, int dtype, const void* Ty, size_t T, size_t ld_in, size_t L, const double* sm, const double* lt, const void* x_in,
-                          void* x, size_t T_state, const LagList& lags, int K, void* ypred, void* out, size_t ld_out, size_t plane_stride, int* status,
-                          int path, hipStream_t stream) {
-    if (L == 0) return;
-    if (T > 0 && path != 1) launch_smooth_forward(d, dtype, Ty, T, ld_in, L, sm, x_in, x, T_state, ypred, ld_out, path, stream);
-    dispatch_stream(d, dtype, [&](auto tv, auto dim) {
+void launch_lagged_stream(int d, const SweepIo& io, const double* sm, const double* lt, size_t T_state, const LagList& lags, const SweepPlanes& out,
+                          int* status, int path) {
+    if (io.L == 0) return;
+    if (io.T > 0 && path != 1) launch_smooth_forward(d, io, sm, T_state, path);
+    dispatch_stream(d, io.dtype, [&](auto tv, auto dim) {
         using Tv = decltype(tv);
         constexpr int D = decltype(dim)::value;
-        if (T > 0 && path != 1) {
+        if (io.T > 0 && path != 1) {
             // lags staged per replay: one for a single lag, else two (four LDS planes per wavefront: 17 KB at fp32, 35 KB at fp64)
-            if (K == 1) launch_bwd_kg<Tv, D, 1>((const Tv*)Ty, T, ld_in, L, sm, lt, lags, K, (const Tv*)ypred, (Tv*)out, ld_out, plane_stride, (Tv*)x, path, stream);
-            else launch_bwd_kg<Tv, D, 2>((const Tv*)Ty, T, ld_in, L, sm, lt, lags, K, (const Tv*)ypred, (Tv*)out, ld_out, plane_stride, (Tv*)x, path, stream);
+            if (out.K == 1) launch_bwd_kg<Tv, D, 1>(io, sm, lt, lags, out, path);
+            else launch_bwd_kg<Tv, D, 2>(io, sm, lt, lags, out, path);
         }
-        hipLaunchKernelGGL((lagged_serial_kernel<Tv, D>), dim3((unsigned)((L + 63) / 64)), dim3(64), 0, stream, (const Tv*)Ty, T, ld_in, sm, lt, L,
-                           (const Tv*)x_in, (Tv*)x, T_state, lags, K, (Tv*)ypred, (Tv*)out, ld_out, plane_stride, status, T > 0 ? path : 1);
+        hipLaunchKernelGGL((lagged_serial_kernel<Tv, D>), dim3((unsigned)((io.L + 63) / 64)), dim3(64), 0, io.stream, (const Tv*)io.Ty, io.T, io.ld, sm, lt,
+                           io.L, (const Tv*)io.xin, (Tv*)io.x, T_state, lags, out.K, (Tv*)io.yhat, (Tv*)out.base, io.ld_out, out.stride, status,
+                           io.T > 0 ? path : 1);
     });
     MOIHGP_HIP_FATAL(hipGetLastError());
 }

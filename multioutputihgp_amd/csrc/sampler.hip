@@ -347,22 +347,23 @@ void launch_sampler_tables(int d, const double* sm, size_t L, double* sp, hipStr
     MOIHGP_HIP_FATAL(hipGetLastError());
 }
 
-void launch_sample_stream(int d, int dtype, size_t T, size_t L, const double* sm, const double* sp, const void* ysm, size_t ld_out, void* samples,
-                          size_t plane_stride, int nsamples, unsigned long long seed, unsigned sample0, unsigned latent0, int* status, int path,
-                          hipStream_t stream) {
-    if (L == 0) return;
-    dispatch_stream(d, dtype, [&](auto tv, auto dim) {
+// The call's record and its planes are unpacked here, at the launch lines.
+void launch_sample_stream(int d, const SweepIo& io, const double* sm, const double* sp, const SweepPlanes& samples, unsigned long long seed,
+                          unsigned sample0, unsigned latent0, int* status, int path) {
+    if (io.L == 0) return;
+    dispatch_stream(d, io.dtype, [&](auto tv, auto dim) {
         using Tv = decltype(tv);
         constexpr int D = decltype(dim)::value;
-        if (T > 0 && path != 1) {
-            const dim3 grid((unsigned)L, (unsigned)((nsamples + kSampleGroup - 1) / kSampleGroup));
-            hipLaunchKernelGGL((sample_sweep_kernel<Tv, D>), grid, dim3(64), 0, stream, sm, sp, T, (const Tv*)ysm, ld_out, (Tv*)samples, plane_stride,
-                               nsamples, seed, sample0, latent0, path);
+        const int nsamples = samples.K;
+        if (io.T > 0 && path != 1) {
+            const dim3 grid((unsigned)io.L, (unsigned)((nsamples + kSampleGroup - 1) / kSampleGroup));
+            hipLaunchKernelGGL((sample_sweep_kernel<Tv, D>), grid, dim3(64), 0, io.stream, sm, sp, io.T, (const Tv*)io.yhat, io.ld_out, (Tv*)samples.base,
+                               samples.stride, nsamples, seed, sample0, latent0, path);
             MOIHGP_HIP_FATAL(hipGetLastError());
         }
-        const size_t n = L * (size_t)nsamples;
-        hipLaunchKernelGGL((sample_serial_kernel<Tv, D>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, sm, sp, L, T, (const Tv*)ysm, ld_out,
-                           (Tv*)samples, plane_stride, nsamples, seed, sample0, latent0, status, T > 0 ? path : 1);
+        const size_t n = io.L * (size_t)nsamples;
+        hipLaunchKernelGGL((sample_serial_kernel<Tv, D>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, io.stream, sm, sp, io.L, io.T, (const Tv*)io.yhat,
+                           io.ld_out, (Tv*)samples.base, samples.stride, nsamples, seed, sample0, latent0, status, io.T > 0 ? path : 1);
         MOIHGP_HIP_FATAL(hipGetLastError());
     });
 }

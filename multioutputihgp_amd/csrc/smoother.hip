@@ -324,36 +324,35 @@ void launch_smoother_tables(int kernel, int d, const double* cb64, size_t L, dou
     MOIHGP_HIP_FATAL(hipGetLastError());
 }
 
+// The call's record is unpacked here, at the launch lines: forward and backward scan sweeps for the latents that take them, then the serial kernel
+// for the rest and the status words.
 template <typename Tv, int D>
-static void launch_smooth_t(const Tv* Ty, size_t T, size_t ld_in, size_t L, const double* tabs, const Tv* x_in, Tv* x, Tv* ys, size_t ld_out,
-                            int* status, int path, hipStream_t stream) {
+static void launch_smooth_t(const SweepIo& io, const double* tabs, int* status, int path) {
+    const Tv *Ty = (const Tv*)io.Ty, *x_in = (const Tv*)io.xin;
+    Tv *x = (Tv*)io.x, *ys = (Tv*)io.yhat;
+    const size_t T = io.T, L = io.L;
     if (T > 0 && path != 1) {
-        hipLaunchKernelGGL((smooth_fwd_kernel<Tv, D, false>), dim3((unsigned)L), dim3(64), 0, stream, Ty, T, ld_in, tabs, x_in, x, ys, ld_out, path, T);
+        hipLaunchKernelGGL((smooth_fwd_kernel<Tv, D, false>), dim3((unsigned)L), dim3(64), 0, io.stream, Ty, T, io.ld, tabs, x_in, x, ys, io.ld_out, path, T);
         MOIHGP_HIP_FATAL(hipGetLastError());
-        hipLaunchKernelGGL((smooth_bwd_kernel<Tv, D>), dim3((unsigned)L), dim3(64), 0, stream, Ty, T, ld_in, tabs, ys, ld_out, path);
+        hipLaunchKernelGGL((smooth_bwd_kernel<Tv, D>), dim3((unsigned)L), dim3(64), 0, io.stream, Ty, T, io.ld, tabs, ys, io.ld_out, path);
         MOIHGP_HIP_FATAL(hipGetLastError());
     }
-    hipLaunchKernelGGL((smooth_serial_kernel<Tv, D>), dim3((unsigned)((L + 63) / 64)), dim3(64), 0, stream, Ty, T, ld_in, tabs, L, x_in, x, ys, ld_out,
+    hipLaunchKernelGGL((smooth_serial_kernel<Tv, D>), dim3((unsigned)((L + 63) / 64)), dim3(64), 0, io.stream, Ty, T, io.ld, tabs, L, x_in, x, ys, io.ld_out,
                        status, T > 0 ? path : 1);
     MOIHGP_HIP_FATAL(hipGetLastError());
 }
 
-void launch_smooth_stream(int d, int dtype, const void* Ty, size_t T, size_t ld_in, size_t L, const double* tabs, const void* x_in, void* x,
-                          void* ys, size_t ld_out, int* status, int path, hipStream_t stream) {
-    if (L == 0) return;
-    dispatch_stream(d, dtype, [&](auto tv, auto dim) {
-        using Tv = decltype(tv);
-        launch_smooth_t<Tv, decltype(dim)::value>((const Tv*)Ty, T, ld_in, L, tabs, (const Tv*)x_in, (Tv*)x, (Tv*)ys, ld_out, status, path, stream);
-    });
+void launch_smooth_stream(int d, const SweepIo& io, const double* tabs, int* status, int path) {
+    if (io.L == 0) return;
+    dispatch_stream(d, io.dtype, [&](auto tv, auto dim) { launch_smooth_t<decltype(tv), decltype(dim)::value>(io, tabs, status, path); });
 }
 
-void launch_smooth_forward(int d, int dtype, const void* Ty, size_t T, size_t ld_in, size_t L, const double* tabs, const void* x_in, void* x,
-                           size_t T_state, void* p, size_t ld_out, int path, hipStream_t stream) {
-    if (L == 0 || T == 0) return;
-    dispatch_stream(d, dtype, [&](auto tv, auto dim) {
+void launch_smooth_forward(int d, const SweepIo& io, const double* tabs, size_t T_state, int path) {
+    if (io.L == 0 || io.T == 0) return;
+    dispatch_stream(d, io.dtype, [&](auto tv, auto dim) {
         using Tv = decltype(tv);
-        hipLaunchKernelGGL((smooth_fwd_kernel<Tv, decltype(dim)::value, true>), dim3((unsigned)L), dim3(64), 0, stream, (const Tv*)Ty, T, ld_in, tabs,
-                           (const Tv*)x_in, (Tv*)x, (Tv*)p, ld_out, path, T_state);
+        hipLaunchKernelGGL((smooth_fwd_kernel<Tv, decltype(dim)::value, true>), dim3((unsigned)io.L), dim3(64), 0, io.stream, (const Tv*)io.Ty, io.T, io.ld,
+                           tabs, (const Tv*)io.xin, (Tv*)io.x, (Tv*)io.yhat, io.ld_out, path, T_state);
     });
     MOIHGP_HIP_FATAL(hipGetLastError());
 }

@@ -85,38 +85,33 @@ def untile_stream(Tt: torch.Tensor, T: int, out: Optional[torch.Tensor] = None, 
 
 
 FORECAST_MAX_HORIZONS = 8       # MOIHGP_FORECAST_MAX_HORIZONS
+LAGGED_MAX_LAGS = 8             # MOIHGP_LAGGED_MAX_LAGS
 _GAINS = {"kalman": 0, "handle": 1}
 
 
-def _forecast_horizons(horizons):
-    """(ctypes int array, K) of a forecast's horizons, validated as include/moihgp.h states them."""
+def _int_list(values, noun: str, most: int):
+    """(ctypes int array, K) of a forecast's horizons (noun "horizon", at most FORECAST_MAX_HORIZONS) or a fixed-lag smoother's lags ("lag",
+    LAGGED_MAX_LAGS), validated as include/moihgp.h states them."""
     try:
-        hs = [h for h in horizons]
+        vs = [v for v in values]
     except TypeError:
-        raise ValueError("horizons must be a sequence of 1 .. 8 integers") from None
-    if not 1 <= len(hs) <= FORECAST_MAX_HORIZONS:
-        raise ValueError(f"the number of horizons ({len(hs)}) must be 1 .. {FORECAST_MAX_HORIZONS}")
-    for h in hs:
-        if isinstance(h, bool) or not isinstance(h, (int, np.integer)) or h < 0 or h > (1 << 20):
-            raise ValueError(f"horizon {h!r} must be an integer in 0 .. 2^20")
-    return (C.c_int * len(hs))(*[int(h) for h in hs]), len(hs)
+        raise ValueError(f"{noun}s must be a sequence of 1 .. 8 integers") from None
+    if not 1 <= len(vs) <= most:
+        raise ValueError(f"the number of {noun}s ({len(vs)}) must be 1 .. {most}")
+    for v in vs:
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0 or v > (1 << 20):
+            raise ValueError(f"{noun} {v!r} must be an integer in 0 .. 2^20")
+    return (C.c_int * len(vs))(*[int(v) for v in vs]), len(vs)
 
 
-LAGGED_MAX_LAGS = 8             # MOIHGP_LAGGED_MAX_LAGS
-
-
-def _lagged_lags(lags):
-    """(ctypes int array, K) of a fixed-lag smoother's lags, validated as include/moihgp.h states them."""
-    try:
-        ls = [h for h in lags]
-    except TypeError:
-        raise ValueError("lags must be a sequence of 1 .. 8 integers") from None
-    if not 1 <= len(ls) <= LAGGED_MAX_LAGS:
-        raise ValueError(f"the number of lags ({len(ls)}) must be 1 .. {LAGGED_MAX_LAGS}")
-    for h in ls:
-        if isinstance(h, bool) or not isinstance(h, (int, np.integer)) or h < 0 or h > (1 << 20):
-            raise ValueError(f"lag {h!r} must be an integer in 0 .. 2^20")
-    return (C.c_int * len(ls))(*[int(h) for h in ls]), len(ls)
+def _row_stride(name: str, buf: torch.Tensor, T: int, Ty: torch.Tensor, also: str = "") -> int:
+    """Row stride a C entry is given for the caller's row buffer `buf` [L, >=T] of the stream Ty, or ValueError (`also`: a further sentence for its text)."""
+    L = Ty.shape[0]
+    if (not buf.is_cuda or buf.dtype != Ty.dtype or buf.dim() != 2 or buf.stride(1) != 1 or buf.shape[0] != L or buf.shape[1] < T
+            or (L > 1 and buf.stride(0) < padded_len(T, Ty.dtype)) or buf.stride(0) % (2 if Ty.dtype == torch.float64 else 4) != 0):
+        raise ValueError(f"{name} must be a CUDA tensor [L, >=T] of the stream's dtype, unit stride along time, row stride a multiple of "
+                         f"16 bytes and >= T rounded up to it{also}")
+    return buf.stride(0) if L > 1 else padded_len(max(T, 1), Ty.dtype)
 
 
 def _forecast_gains(gains) -> int:
@@ -256,11 +251,8 @@ class LatentBank:
         if want_yhat:
             if yhat is None:
                 yhat = self._like_stream(Ty)
-            elif (not yhat.is_cuda or yhat.dtype != Ty.dtype or yhat.dim() != 2 or yhat.stride(1) != 1
-                  or yhat.shape[0] != self.L or yhat.shape[1] < T or (self.L > 1 and yhat.stride(0) < padded_len(T, Ty.dtype))
-                  or yhat.stride(0) % (2 if Ty.dtype == torch.float64 else 4) != 0):
-                raise ValueError("yhat must be a CUDA tensor [L, >=T] of the stream's dtype, unit stride along time, row stride a multiple of "
-                                 "16 bytes and >= T rounded up to it (it need not equal the stream's: moihgp_filter_stream_v2 takes both)")
+            else:
+                _row_stride("yhat", yhat, T, Ty, " (it need not equal the stream's: moihgp_filter_stream_v2 takes both)")
         if x.dtype != Ty.dtype or not x.is_contiguous() or tuple(x.shape) != (self.L, self.d):
             raise ValueError("x must be a contiguous [L, d] tensor of the stream dtype")
         if want_nll and nll is None:
@@ -341,12 +333,32 @@ class LatentBank:
         """(ysmooth, ld_out) of smooth / sample: the caller's buffer, checked, or a fresh one."""
         if ysmooth is None:
             ysmooth = alloc_stream(self.L, max(T, 1), Ty.dtype, Ty.device)[:, :T]
-        elif (not ysmooth.is_cuda or ysmooth.dtype != Ty.dtype or ysmooth.dim() != 2 or ysmooth.stride(1) != 1 or ysmooth.shape[0] != self.L
-              or ysmooth.shape[1] < T or (self.L > 1 and ysmooth.stride(0) < padded_len(T, Ty.dtype))
-              or ysmooth.stride(0) % (2 if Ty.dtype == torch.float64 else 4) != 0):
-            raise ValueError("ysmooth must be a CUDA tensor [L, >=T] of the stream's dtype, unit stride along time, row stride a multiple of "
-                             "16 bytes and >= T rounded up to it")
-        return ysmooth, (ysmooth.stride(0) if self.L > 1 else padded_len(max(T, 1), Ty.dtype))
+        return ysmooth, _row_stride("ysmooth", ysmooth, T, Ty)
+
+    def _plane_and_row_buffers(self, Ty: torch.Tensor, T: int, K: int, out: Optional[torch.Tensor], rows: Optional[torch.Tensor]):
+        """(out, ld_out, plane, rows, hand_over) of sample / lagged, which write K planes `out` [K, L, >=T] and a row buffer `rows` [L, >=T] (ysmooth,
+        ypred): the caller's buffers, checked, or fresh ones.  One row stride serves both buffers in the C entry: rows without a buffer of their own
+        take the planes' stride, and a caller's `rows` of another stride is replaced by a buffer of that stride for the call; hand_over(stream),
+        called behind the sweep, copies it into the caller's tensor and returns the tensor to hand back."""
+        if out is None:
+            rows, ld_out = self._ysmooth_buffer(Ty, T, rows)
+            out = torch.empty((K, self.L, ld_out), dtype=Ty.dtype, device=Ty.device)[:, :, :T]
+        ld_out, plane = _plane_out_strides(out, K, self.L, T, Ty)
+        mine = rows
+        if rows is None or (self._ysmooth_buffer(Ty, T, rows)[1] != ld_out and self.L > 1):
+            mine = torch.empty((self.L, ld_out), dtype=Ty.dtype, device=Ty.device)[:, :T]
+
+        def hand_over(stream):
+            if rows is None or mine is rows:
+                return mine
+            with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
+                rows[:, :T].copy_(mine)
+            return rows
+        return out, ld_out, plane, mine, hand_over
+
+    def _refuse_stacked(self, who: str):
+        if self.stacked:
+            raise MoihgpError(f"{who}: stacked models are not supported (Matern-3/2 and -5/2 only)", 3)
 
     def smooth(self, Ty: torch.Tensor, T: Optional[int] = None, x: Optional[torch.Tensor] = None, x_start: Optional[torch.Tensor] = None,
                ysmooth: Optional[torch.Tensor] = None, stream=None):
@@ -357,8 +369,7 @@ class LatentBank:
         Asynchronous on the current torch stream.  The sweep starts from `x_start` if given, else from `x`, else from zeros; `x` receives the
         end state in place.  `ysmooth` (optional) must not overlap Ty; its row stride may differ from the stream's."""
         T, ld = self._check_stream(Ty, T)
-        if self.stacked:
-            raise MoihgpError("smooth: stacked models are not supported (Matern-3/2 and -5/2 only)", 3)
+        self._refuse_stacked("smooth")
         x, start = self._start_state(Ty, x, x_start)
         ysmooth, ld_out = self._ysmooth_buffer(Ty, T, ysmooth)
         status = torch.empty((self.L,), dtype=torch.int32, device=Ty.device)
@@ -402,31 +413,16 @@ class LatentBank:
         seed, sample0, latent0 = int(seed), int(sample0), int(latent0)
         if not (0 <= seed < 1 << 64 and 0 <= sample0 < 1 << 32 and 0 <= latent0 < 1 << 32):
             raise ValueError("seed must be in 0 .. 2^64 - 1, sample0 and latent0 in 0 .. 2^32 - 1")
-        if self.stacked:
-            raise MoihgpError("sample: stacked models are not supported (Matern-3/2 and -5/2 only)", 3)
+        self._refuse_stacked("sample")
         x, start = self._start_state(Ty, x, x_start)
-        if out is None:
-            ysmooth, ld_out = self._ysmooth_buffer(Ty, T, ysmooth)
-            out = torch.empty((S, self.L, ld_out), dtype=Ty.dtype, device=Ty.device)[:, :, :T]
-        ld_out, plane = _plane_out_strides(out, S, self.L, T, Ty)
-        # one row stride serves both buffers in the C entry: means without a buffer of their own take the sample planes' stride, and a caller's
-        # `ysmooth` of another stride receives a copy
-        ys_user = None
-        if ysmooth is None:
-            ysmooth = torch.empty((self.L, ld_out), dtype=Ty.dtype, device=Ty.device)[:, :T]
-        elif self._ysmooth_buffer(Ty, T, ysmooth)[1] != ld_out and self.L > 1:
-            ys_user, ysmooth = ysmooth, torch.empty((self.L, ld_out), dtype=Ty.dtype, device=Ty.device)[:, :T]
+        out, ld_out, plane, ysmooth, hand_over = self._plane_and_row_buffers(Ty, T, S, out, ysmooth)
         status = torch.empty((self.L,), dtype=torch.int32, device=Ty.device)
         rc = self._lib.moihgp_sample_stream(self._h, _DT[Ty.dtype], C.c_void_p(Ty.data_ptr()), T, ld,
                                             C.c_void_p(start.data_ptr()), C.c_void_p(x.data_ptr()), S, seed, sample0, latent0,
                                             C.c_void_p(ysmooth.data_ptr()), ld_out, C.c_void_p(out.data_ptr()), plane,
                                             C.c_void_p(status.data_ptr()), _stream_ptr(stream))
         _check(rc, self._lib)
-        if ys_user is not None:
-            with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
-                ys_user[:, :T].copy_(ysmooth)
-            ysmooth = ys_user
-        return out, ysmooth, x, status
+        return out, hand_over(stream), x, status
 
     def sampler(self, l: int) -> dict:
         """The sampler's realization of latent l (moihgp_get_sampler): B, sigma2, Sigma, Lc, acov_err, status."""
@@ -451,10 +447,9 @@ class LatentBank:
         Asynchronous on the current torch stream.  The sweep starts from `x_start` if given, else from `x`, else from zeros; `x` receives the end
         state in place.  `out` (optional) [K, L, >=T] must not overlap Ty; row and plane strides multiples of 16 bytes."""
         T, ld = self._check_stream(Ty, T)
-        hz, K = _forecast_horizons(horizons)
+        hz, K = _int_list(horizons, "horizon", FORECAST_MAX_HORIZONS)
         g = _forecast_gains(gains)
-        if self.stacked:
-            raise MoihgpError("forecast: stacked models are not supported (Matern-3/2 and -5/2 only)", 3)
+        self._refuse_stacked("forecast")
         x, start = self._start_state(Ty, x, x_start)
         if out is None:
             out = torch.empty((K, self.L, padded_len(max(T, 1), Ty.dtype)), dtype=Ty.dtype, device=Ty.device)[:, :, :T]
@@ -479,40 +474,26 @@ class LatentBank:
         first t1 - t0 ticks of every plane and carry `x`.  `out` (optional) [K, L, >=T] as forecast()'s, `ypred` (optional) as smooth()'s
         `ysmooth`; `out`, `ypred` and Ty must not overlap each other."""
         T, ld = self._check_stream(Ty, T)
-        lg, K = _lagged_lags(lags)
+        lg, K = _int_list(lags, "lag", LAGGED_MAX_LAGS)
         state_at = T if state_at is None else state_at
         if isinstance(state_at, bool) or not isinstance(state_at, (int, np.integer)) or not 0 <= state_at <= T:
             raise ValueError(f"state_at {state_at!r} must be an integer in 0 .. T")
-        if self.stacked:
-            raise MoihgpError("lagged: stacked models are not supported (Matern-3/2 and -5/2 only)", 3)
+        self._refuse_stacked("lagged")
         x, start = self._start_state(Ty, x, x_start)
-        if out is None:
-            ypred, ld_out = self._ysmooth_buffer(Ty, T, ypred)
-            out = torch.empty((K, self.L, ld_out), dtype=Ty.dtype, device=Ty.device)[:, :, :T]
-        ld_out, plane = _plane_out_strides(out, K, self.L, T, Ty)
-        # one row stride serves both buffers in the C entry (as in sample()): a caller's `ypred` of another stride receives a copy
-        yp_user = None
-        if ypred is None:
-            ypred = torch.empty((self.L, ld_out), dtype=Ty.dtype, device=Ty.device)[:, :T]
-        elif self._ysmooth_buffer(Ty, T, ypred)[1] != ld_out and self.L > 1:
-            yp_user, ypred = ypred, torch.empty((self.L, ld_out), dtype=Ty.dtype, device=Ty.device)[:, :T]
+        out, ld_out, plane, ypred, hand_over = self._plane_and_row_buffers(Ty, T, K, out, ypred)
         status = torch.empty((self.L,), dtype=torch.int32, device=Ty.device)
         rc = self._lib.moihgp_lagged_stream(self._h, _DT[Ty.dtype], C.c_void_p(Ty.data_ptr()), T, ld,
                                             C.c_void_p(start.data_ptr()), C.c_void_p(x.data_ptr()), int(state_at), lg, K,
                                             C.c_void_p(ypred.data_ptr()), C.c_void_p(out.data_ptr()), ld_out, plane,
                                             C.c_void_p(status.data_ptr()), _stream_ptr(stream))
         _check(rc, self._lib)
-        if yp_user is not None:
-            with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
-                yp_user[:, :T].copy_(ypred)
-            ypred = yp_user
-        return out, ypred, x, status
+        return out, hand_over(stream), x, status
 
     def lagged_variances(self, lags) -> np.ndarray:
         """var [K, L] (moihgp_lagged_variances), fp64 numpy: the steady-state variance of the latent function at tick t given the ticks <= t + lag
         (add the noise parameter for an observation): var_filtered at lag 0, falling to var_smoothed; NaN for a latent whose Kalman DARE did not
         converge."""
-        lg, K = _lagged_lags(lags)
+        lg, K = _int_list(lags, "lag", LAGGED_MAX_LAGS)
         var = np.zeros((K, self.L))
         _check(self._lib.moihgp_lagged_variances(self._h, lg, K, var.ctypes.data_as(c_double_p)), self._lib)
         return var
@@ -524,8 +505,7 @@ class LatentBank:
             raise ValueError("n must be 0 .. 2^20")
         if x.dtype not in _DT or not x.is_contiguous() or tuple(x.shape) != (self.L, self.d):
             raise ValueError("x must be a contiguous [L, d] tensor (float32/float64)")
-        if self.stacked:
-            raise MoihgpError("forecast: stacked models are not supported (Matern-3/2 and -5/2 only)", 3)
+        self._refuse_stacked("forecast")
         tail = alloc_stream(self.L, max(n, 1), x.dtype, x.device)
         _check(self._lib.moihgp_forecast_tail(self._h, _DT[x.dtype], C.c_void_p(x.data_ptr()), n, C.c_void_p(tail.data_ptr()), tail.stride(0),
                                               _stream_ptr(stream)), self._lib)
@@ -534,7 +514,7 @@ class LatentBank:
     def forecast_variances(self, horizons) -> np.ndarray:
         """var [K, L] (moihgp_forecast_variances), fp64 numpy: the steady-state variance of the latent function at t + h given the ticks <= t, which
         belongs to the "kalman" gains (add the noise parameter for an observation); NaN for a latent whose Kalman DARE did not converge."""
-        hz, K = _forecast_horizons(horizons)
+        hz, K = _int_list(horizons, "horizon", FORECAST_MAX_HORIZONS)
         var = np.zeros((K, self.L))
         _check(self._lib.moihgp_forecast_variances(self._h, hz, K, var.ctypes.data_as(c_double_p)), self._lib)
         return var
@@ -640,6 +620,18 @@ def filter_outputs(gp, Y: torch.Tensor, layout: str = "auto", want_nll: bool = T
         return unproject_stream(gp, yhat, T, stream=stream), x, nll
 
 
+def _output_variances(gp, var: np.ndarray, bad, message: str) -> np.ndarray:
+    """The tail of the *_outputs functions: MoihgpError(message) where `bad` says that a latent failed, else var_Y[..., m] = sum_l U[m, l]^2 S_l var[..., l]
+    from the latents' variances var [L] or [K, L] and the mixing in gp.params."""
+    if bad:
+        raise MoihgpError(message, 1)
+    M, L = gp.num_output, gp.num_latent
+    prm = gp.params
+    U, S = prm[:M * L].reshape(M, L), prm[M * L:M * L + L]
+    w = S * var
+    return (U ** 2) @ w if w.ndim == 1 else w @ (U ** 2).T      # (the two products as they have always been taken: no last-bit change)
+
+
 def smooth_outputs(gp, Y: torch.Tensor, stream=None):
     """Smoothed outputs of a tick-major observation stream Y [T, M] (NaN = missing output) with the parameters of `gp` (a pywrapper.MOIHGP):
     project_stream -> LatentBank.smooth -> unproject_stream, from a zero state.
@@ -654,14 +646,8 @@ def smooth_outputs(gp, Y: torch.Tensor, stream=None):
     ys, _, status = bank.smooth(Ty, T=T, stream=stream)
     Ys = unproject_stream(gp, ys, T, stream=stream)
     bad = int((status != 0).sum())      # (synchronises)
-    if bad:
-        raise MoihgpError(f"smooth_outputs: the Kalman DARE of {bad} latent(s) did not converge; their rows are NaN and so is every output "
-                          "that mixes them", 1)
-    M, L = gp.num_output, gp.num_latent
-    prm = gp.params
-    U, S = prm[:M * L].reshape(M, L), prm[M * L:M * L + L]
-    _, vs = bank.latent_variances()
-    return Ys, (U ** 2) @ (S * vs)
+    return Ys, _output_variances(gp, bank.latent_variances()[1], bad, f"smooth_outputs: the Kalman DARE of {bad} latent(s) did not converge; their rows "
+                                 "are NaN and so is every output that mixes them")
 
 
 def sample_noise(seed: int, L: int, S: int, T: int, latent0: int = 0, sample0: int = 0, want_start: bool = True, device="cuda", stream=None):
@@ -690,14 +676,9 @@ def sample_outputs(gp, Y: torch.Tensor, nsamples: int, seed: int = 0, stream=Non
     Ys = torch.stack([unproject_stream(gp, smp[s], T, stream=stream) for s in range(smp.shape[0])])
     Ymean = unproject_stream(gp, ys, T, stream=stream)
     st = status.cpu().numpy()           # (synchronises)
-    if st.any():
-        raise MoihgpError(f"sample_outputs: {int((st == 1).sum())} latent(s) whose Kalman DARE did not converge, {int((st == 2).sum())} whose "
-                          "sampling realization was not accepted; their rows are NaN and so is every output that mixes them", 1)
-    M, L = gp.num_output, gp.num_latent
-    prm = gp.params
-    U, S = prm[:M * L].reshape(M, L), prm[M * L:M * L + L]
-    _, vs = bank.latent_variances()
-    return Ys, Ymean, (U ** 2) @ (S * vs)
+    return Ys, Ymean, _output_variances(gp, bank.latent_variances()[1], st.any(), f"sample_outputs: {int((st == 1).sum())} latent(s) whose Kalman DARE "
+                                        f"did not converge, {int((st == 2).sum())} whose sampling realization was not accepted; their rows are NaN and "
+                                        "so is every output that mixes them")
 
 
 def forecast_outputs(gp, Y: torch.Tensor, horizons, tail: int = 0, gains: str = "kalman", stream=None):
@@ -712,7 +693,7 @@ def forecast_outputs(gp, Y: torch.Tensor, horizons, tail: int = 0, gains: str = 
     than L observed ones is treated as missing as a whole."""
     T = Y.shape[0]
     bank = LatentBank.from_handle(gp)
-    _, K = _forecast_horizons(horizons)
+    _, K = _int_list(horizons, "horizon", FORECAST_MAX_HORIZONS)
     Ty = project_stream(gp, Y, stream=stream)
     fc, x, status = bank.forecast(Ty, horizons, T=T, gains=gains, stream=stream)
     Yf = torch.stack([unproject_stream(gp, fc[k], T, stream=stream) for k in range(K)])
@@ -721,13 +702,9 @@ def forecast_outputs(gp, Y: torch.Tensor, horizons, tail: int = 0, gains: str = 
         Ytail = unproject_stream(gp, bank.forecast_tail(x, tail, stream=stream), tail, stream=stream)
     var = bank.forecast_variances(horizons)      # (synchronises)
     bad = int(((status != 0).cpu().numpy() | np.isnan(var).any(axis=0)).sum())
-    if bad:      # (with gains "handle" the means exist, but var_Y does not)
-        raise MoihgpError(f"forecast_outputs: the Kalman DARE of {bad} latent(s) did not converge; their rows and variances are NaN and so is "
-                          "every output that mixes them", 1)
-    M, L = gp.num_output, gp.num_latent
-    prm = gp.params
-    U, S = prm[:M * L].reshape(M, L), prm[M * L:M * L + L]
-    return Yf, (S[None, :] * var) @ (U ** 2).T, Ytail
+    # (with gains "handle" the means exist, but var_Y does not)
+    return Yf, _output_variances(gp, var, bad, f"forecast_outputs: the Kalman DARE of {bad} latent(s) did not converge; their rows and variances are NaN "
+                                 "and so is every output that mixes them"), Ytail
 
 
 def lagged_outputs(gp, Y: torch.Tensor, lags, stream=None):
@@ -740,16 +717,11 @@ def lagged_outputs(gp, Y: torch.Tensor, lags, stream=None):
     project_stream does it: a tick with more than 64 missing outputs or fewer than L observed ones is treated as missing as a whole."""
     T = Y.shape[0]
     bank = LatentBank.from_handle(gp)
-    _, K = _lagged_lags(lags)
+    _, K = _int_list(lags, "lag", LAGGED_MAX_LAGS)
     Ty = project_stream(gp, Y, stream=stream)
     lg, _, _, status = bank.lagged(Ty, lags, T=T, stream=stream)
     Yl = torch.stack([unproject_stream(gp, lg[k], T, stream=stream) for k in range(K)])
     var = bank.lagged_variances(lags)      # (synchronises)
     bad = int(((status != 0).cpu().numpy() | np.isnan(var).any(axis=0)).sum())
-    if bad:
-        raise MoihgpError(f"lagged_outputs: the Kalman DARE of {bad} latent(s) did not converge; their rows and variances are NaN and so is "
-                          "every output that mixes them", 1)
-    M, L = gp.num_output, gp.num_latent
-    prm = gp.params
-    U, S = prm[:M * L].reshape(M, L), prm[M * L:M * L + L]
-    return Yl, (S[None, :] * var) @ (U ** 2).T
+    return Yl, _output_variances(gp, var, bad, f"lagged_outputs: the Kalman DARE of {bad} latent(s) did not converge; their rows and variances are NaN "
+                                 "and so is every output that mixes them")

@@ -164,11 +164,11 @@ def test_numpy_variance_starts_at_var_filtered_and_rises_to_the_prior(kern):
 def test_python_argument_validation():
     import torch
     from multioutputihgp_amd import streams
-    hz, K = streams._forecast_horizons(HORIZONS)
+    hz, K = streams._int_list(HORIZONS, "horizon", streams.FORECAST_MAX_HORIZONS)
     assert K == 6 and list(hz) == HORIZONS
     for bad in ([], list(range(9)), [-1], [HMAX + 1], [1.5], [True], 3, None):
         with pytest.raises(ValueError):
-            streams._forecast_horizons(bad)
+            streams._int_list(bad, "horizon", streams.FORECAST_MAX_HORIZONS)
     with pytest.raises(ValueError):
         streams._forecast_gains("literal")
     assert streams._forecast_gains("kalman") == 0 and streams._forecast_gains("handle") == 1

@@ -188,8 +188,8 @@ def test_python_argument_validation():
     from multioutputihgp_amd import streams
     for bad in ([], list(range(9)), [-1], [LMAX + 1], [1.5], [True], 3):
         with pytest.raises(ValueError):
-            streams._lagged_lags(bad)
-    arr, K = streams._lagged_lags(np.array([3, 0, LMAX]))
+            streams._int_list(bad, "lag", streams.LAGGED_MAX_LAGS)
+    arr, K = streams._int_list(np.array([3, 0, LMAX]), "lag", streams.LAGGED_MAX_LAGS)
     assert K == 3 and list(arr) == [3, 0, LMAX]
 
 
@@ -275,6 +275,35 @@ def test_lagged_parity(env, kern, L, T, dtype, gaps):
         assert ep <= tol_of(dtype) and ex <= tol_of(dtype), (ep, ex)
         assert padding_untouched(torch, slab, out) and padding_untouched(torch, yslab, yp)
         assert ypred.data_ptr() == yp.data_ptr()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+def test_ypred_on_another_row_stride_than_out(env, dtype):
+    """The C entry takes one row stride for both buffers, so lagged() sweeps into a buffer of the planes' stride and copies it into a caller's `ypred`
+    of another stride: the caller's tensor comes back, bit-equal to a call without the copy, and nothing between its rows is written.  L = 3 (one
+    latent has no row stride), T = 17: one ragged 16-tick chunk."""
+    torch, streams = env["torch"], env["streams"]
+    tdt = torch.float64 if dtype == "f64" else torch.float32
+    L, T, lags, vec = 3, 17, [0, 3], 16 // (8 if dtype == "f64" else 4)
+    ld = streams.padded_len(T, tdt)
+    bank, _, _ = bank_and_tables(streams, "Matern52", L)
+    dev = to_dev(torch, synth(L, T, np.random.default_rng(23)), tdt, T)
+
+    def carve(K, ldo):
+        slab = torch.full((K * L * ldo + 16,), 12345.0, dtype=tdt, device="cuda")
+        return slab, torch.as_strided(slab, (K, L, T), (L * ldo, ldo, 1), 0)
+    res = []
+    for ld_yp in (ld + 2 * vec, ld + vec):          # ypred rows two vectors longer than T rounded up, then of out's stride: one more
+        oslab, out = carve(len(lags), ld + vec)
+        yslab, yp3 = carve(1, ld_yp)
+        lg, ypred, _, status = bank.lagged(dev, lags, out=out, ypred=yp3[0])
+        torch.cuda.synchronize()
+        assert int(status.abs().sum()) == 0
+        assert lg.data_ptr() == out.data_ptr() and ypred.data_ptr() == yp3.data_ptr() and ypred.stride(0) == ld_yp
+        assert padding_untouched(torch, oslab, out) and padding_untouched(torch, yslab, yp3)
+        res.append((ypred.cpu().numpy(), lg.cpu().numpy()))
+    assert np.isfinite(res[0][0]).all() and np.array_equal(res[0][0], res[1][0]) and np.array_equal(res[0][1], res[1][1])
 
 
 @pytest.mark.gpu
