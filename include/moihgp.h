@@ -307,6 +307,35 @@ int moihgp_forecast_stream(moihgp_gp* gp, int dtype, const void* Ty, size_t T, s
 int moihgp_forecast_tail(moihgp_gp* gp, int dtype, const void* x, size_t n, void* tail, size_t ld_out, void* stream);
 int moihgp_forecast_variances(moihgp_gp* gp, const int* horizons, size_t K, double* var);
 
+/* ---- forecast scores: backtest errors of those forecasts on the stream itself, per latent and horizon (not in the reference) ---------------------
+ * The gains, the recursion x[t] and fc[k][l][t] = H A^{h_k} x_l[t] are exactly moihgp_forecast_stream's, and so are the rules for the horizons
+ * (1 .. MOIHGP_FORECAST_MAX_HORIZONS integers in 0 .. 2^20, in any order, repeats allowed).  No plane is written: every forecast is held against the
+ * observation it predicts and only sums leave.  For each horizon k and latent l, over the origins t_first <= t < T:
+ *     e = y[t + h_k] - fc[k][l][t]           scored iff t + h_k < T and y[t + h_k] is not NaN
+ *     n[k][l] = number of scored origins,   sum_err[k][l] = sum of e,   sum_sq[k][l] = sum of e^2
+ * The origin tick itself may be missing: the forecast is made there anyway, as moihgp_forecast_stream makes it.  t_first skips the start-up
+ * transient of a zero start state.  h = 0 scores the in-sample residual y[t] - H x[t], the observation against the filtered mean it has already
+ * moved: that is NOT a prediction error.  The states and the forecasts are computed in the stream's own precision, as the forecast sweep computes
+ * them, and e is formed in it; the sums are accumulated in fp64 for both stream types, in a fixed order: two calls with the same arguments give
+ * the same bits.
+ * With the Kalman gains also
+ *     pvar[k][l] = var[k][l] + R_l           var of moihgp_forecast_variances, R_l the latent's noise parameter
+ * the steady-state predictive variance of an OBSERVATION at t + h_k given the ticks <= t, for h_k >= 1 (at h = 1 it is S = P_00 + R of the smoother's
+ * tables, exactly: Pinf - A (Pinf - PF) A^T = P).  sum_sq / (n pvar) is then ~ 1 for a calibrated model, and
+ * -1/2 (n log(2 pi pvar) + sum_sq / pvar) at h = 1 is the steady-state marginal log likelihood of the textbook Kalman filter over the scored ticks
+ * (the learners' NLL, which keeps the reference's literal DARE, is moihgp_filter_stream's and is not this).
+ * moihgp_forecast_scores: n (long long), sum_err, sum_sq, pvar (double) are DEVICE arrays [K][L]; sum_err and pvar may be NULL.  Ty, x_in, x, ld_in,
+ *   alignment, asynchrony and stream bookkeeping as moihgp_forecast_stream; x receives the end state (x_in == x allowed).  horizons: HOST int [K],
+ *   read before the call returns.  status: DEVICE int [L] or NULL.  The smoother's tables are built when moihgp_forecast_stream would build them.
+ *   gains = 0: a latent whose Kalman DARE did not converge gets status 1, n = 0, NaN sums, NaN pvar and a NaN end state.  gains = 1: status is all
+ *   zero, pvar must be NULL (the variances belong to the Kalman gains), and an unstable latent's sums are whatever the arithmetic gives (inf or NaN
+ *   allowed).  T = 0 gives zeros and x = x_in.  Option "forecast_path" governs the route as it does for moihgp_forecast_stream (latents that fail the
+ *   growth bound take the serial fp64 walk).  Returns 1 (and launches nothing) for K or a horizon out of range, unknown gains, t_first > T, a NULL n
+ *   or sum_sq, pvar given with MOIHGP_GAINS_HANDLE; 3 for stacked models. */
+int moihgp_forecast_scores(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x,
+                           const int* horizons, size_t K, size_t t_first, int gains,
+                           long long* n, double* sum_err, double* sum_sq, double* pvar, int* status, void* stream);
+
 /* ---- fixed-lag smoothing of whole streams, with variances (not in the reference) -------------------------------------------------------------
  * The mean of every latent at tick t given the ticks up to t + l: what an online caller knows about tick t once it has waited l more ticks.  It
  * is the member of the family between the filtered mean (l = 0: moihgp_forecast_stream with h = 0 and the Kalman gains) and the smoothed one

@@ -24,7 +24,7 @@ ADDITIVE_SYMBOLS = [
     "moihgp_profile_enable", "moihgp_profile_stride", "moihgp_profile_read", "moihgp_window_set", "moihgp_window_eval", "moihgp_pin_host_buffer",
     "moihgp_update_dev", "moihgp_window_eval_dev", "moihgp_update_dev_on", "moihgp_window_eval_dev_on", "moihgp_get_params_dev", "moihgp_set_option", "moihgp_release_stream",
     "moihgp_ls_shard_gram", "moihgp_ls_shard_apply", "moihgp_smooth_stream", "moihgp_get_smoother", "moihgp_latent_variances",
-    "moihgp_forecast_stream", "moihgp_forecast_tail", "moihgp_forecast_variances",
+    "moihgp_forecast_stream", "moihgp_forecast_tail", "moihgp_forecast_variances", "moihgp_forecast_scores",
     "moihgp_lagged_stream", "moihgp_lagged_variances",
     "moihgp_sample_stream", "moihgp_sample_noise", "moihgp_get_sampler",
     "moihgp_dvec_ctx_new", "moihgp_dvec_ctx_del", "moihgp_dvec_ctx_stream", "moihgp_dvec_alloc", "moihgp_dvec_alloc_mask", "moihgp_dvec_free", "moihgp_dvec_trim", "moihgp_dvec_cache_limit", "moihgp_dvec_upload", "moihgp_dvec_download",
@@ -169,6 +169,9 @@ def load_library():
     lib.moihgp_get_sampler.argtypes = [C.c_void_p, C.c_size_t] + [c_double_p] * 5 + [C.POINTER(C.c_int)]
     lib.moihgp_forecast_variances.restype = C.c_int
     lib.moihgp_forecast_variances.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_size_t, c_double_p]
+    lib.moihgp_forecast_scores.restype = C.c_int
+    lib.moihgp_forecast_scores.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_size_t,
+                                           C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.moihgp_lagged_stream.restype = C.c_int
     lib.moihgp_lagged_stream.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int),
                                          C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]

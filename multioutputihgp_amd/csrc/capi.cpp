@@ -1252,6 +1252,33 @@ static int forecast_variances_impl(moihgp_gp* gp, const int* horizons, size_t K,
                                [&] { build_forecast_tables(gp, hz, K, MOIHGP_GAINS_KALMAN, gp->stream); });
 }
 
+// The forecasts of forecast_stream_impl held against the stream itself: per (horizon, latent) sums instead of planes, so there are no output rows to check.
+static int forecast_scores_impl(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x, const int* horizons, size_t K,
+                                size_t t_first, int gains, long long* n, double* sum_err, double* sum_sq, double* pvar, int* status, void* stream) {
+    if (int rc = check_sweep_call(gp, dtype, Ty, T, ld_in, x_in, x)) return rc;
+    FcHorizons hz;
+    if (int rc = check_int_list("forecast_scores", "horizon", horizons, K, MOIHGP_FORECAST_MAX_HORIZONS, hz.h)) return rc;
+    if (gains != MOIHGP_GAINS_KALMAN && gains != MOIHGP_GAINS_HANDLE) { set_last_error("forecast_scores: gains must be MOIHGP_GAINS_KALMAN (0) or MOIHGP_GAINS_HANDLE (1)"); return 1; }
+    if (t_first > T) { set_last_error("forecast_scores: t_first (%zu) must be <= T (%zu)", t_first, T); return 1; }
+    if (!n || !sum_sq) { set_last_error("forecast_scores: null n / sum_sq buffer"); return 1; }
+    if (pvar && gains != MOIHGP_GAINS_KALMAN) { set_last_error("forecast_scores: pvar belongs to MOIHGP_GAINS_KALMAN; pass NULL with the handle's gains"); return 1; }
+    if (kernel_stack(gp->kernel)) { set_last_error("forecast: stacked models are not supported (Matern-3/2 and -5/2 only)"); return 3; }
+    const SweepIo io = stream_sweep_io(gp, dtype, Ty, T, ld_in, x_in, x, nullptr, 0, stream);
+    if (gains == MOIHGP_GAINS_KALMAN)
+        if (int rc = ensure_smoother(gp, io.stream)) return rc;
+    note_user_stream(gp, io.stream);
+    build_forecast_tables(gp, hz, K, gains, io.stream);
+    launch_forecast_scores(gp->d, io, gp->fc.d64, gp->fc.d32, gp->cb64, hz, (int)K, t_first, ScoreSums{n, sum_err, sum_sq, pvar}, status, gp->opt_forecast_path);
+    call_tables_end(gp->fc, io.stream);
+    return 0;
+}
+
+int moihgp_forecast_scores(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x, const int* horizons, size_t K,
+                           size_t t_first, int gains, long long* n, double* sum_err, double* sum_sq, double* pvar, int* status, void* stream) {
+    return guard_rc([&] {
+        return forecast_scores_impl(gp, dtype, Ty, T, ld_in, x_in, x, horizons, K, t_first, gains, n, sum_err, sum_sq, pvar, status, stream);
+    });
+}
 int moihgp_forecast_stream(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x, const int* horizons, size_t K,
                            void* fc, size_t ld_out, size_t plane_stride, int gains, int* status, void* stream) {
     return guard_rc([&] { return forecast_stream_impl(gp, dtype, Ty, T, ld_in, x_in, x, horizons, K, fc, ld_out, plane_stride, gains, status, stream); });

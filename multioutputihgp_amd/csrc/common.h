@@ -255,6 +255,14 @@ void launch_forecast_tables(int kernel, int d, const double* cb64, const double*
 // every latent
 void launch_forecast_stream(int d, const SweepIo& io, const double* t64, const float* t32, const SweepPlanes& fc, int* status, int path);
 void launch_forecast_tail(int d, int dtype, const double* cb64, size_t L, const void* x, size_t n, void* tail, size_t ld_out, hipStream_t stream);
+// The backtest sums of moihgp_forecast_scores, device arrays [K][L]: sum_err and pvar may be NULL.  The tables are launch_forecast_tables' for the
+// call's horizons hz; cb64 gives the latents' noise parameter for pvar; origins from t_first on are scored; path as launch_forecast_stream's.
+struct ScoreSums {
+    long long* n;
+    double *sum_err, *sum_sq, *pvar;
+};
+void launch_forecast_scores(int d, const SweepIo& io, const double* t64, const float* t32, const double* cb64, const FcHorizons& hz, int K, size_t t_first,
+                            const ScoreSums& out, int* status, int path);
 // lagged.hip: fixed-lag smoothing (include/moihgp.h moihgp_lagged_stream).  Per-latent fp64 block LT<D> of lt_size(d) doubles (stream_tables.h), built per
 // call for the call's lags from the smoother's blocks sm, which the sweeps read beside it.  io.yhat (ypred) receives the forward pass's predicted
 // means, out the K planes; io.x the filtered state after tick T_state - 1.  path as launch_smooth_stream's.

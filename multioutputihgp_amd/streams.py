@@ -120,6 +120,13 @@ def _forecast_gains(gains) -> int:
     return _GAINS[gains]
 
 
+def _first_origin(t_first, T: int) -> int:
+    """t_first of forecast_scores: an integer in 0 .. T, or ValueError."""
+    if isinstance(t_first, bool) or not isinstance(t_first, (int, np.integer)) or not 0 <= t_first <= T:
+        raise ValueError(f"t_first {t_first!r} must be an integer in 0 .. T ({T})")
+    return int(t_first)
+
+
 def _plane_out_strides(out: torch.Tensor, K: int, L: int, T: int, Ty: torch.Tensor):
     """(ld_out, plane_stride) of a buffer of K planes [K, L, >=T] (forecast horizons, posterior samples) for the stream Ty, or ValueError:
     dtype, device, shape, unit stride along time, row and plane strides multiples of 16 bytes, rows >= T rounded up, planes >= L rows, and no overlap with Ty."""
@@ -461,6 +468,37 @@ class LatentBank:
         _check(rc, self._lib)
         return out, x, status
 
+    def forecast_scores(self, Ty: torch.Tensor, horizons, T: Optional[int] = None, t_first: int = 0, x: Optional[torch.Tensor] = None,
+                        x_start: Optional[torch.Tensor] = None, gains: str = "kalman", stream=None) -> dict:
+        """Backtest errors of forecast()'s forecasts on the stream itself (include/moihgp.h moihgp_forecast_scores), without writing a plane: for
+        every horizon k and latent l, over the origins t_first <= t < T whose target tick t + horizons[k] lies inside the stream and is observed,
+        e = Ty[l, t + h] - fc[k, l, t]; n counts them, sum_err and sum_sq add e and e^2 in fp64 in a fixed order (two equal calls give equal bits).
+        The origin tick itself may be missing.  `t_first` skips the start-up transient of a zero start state.  h = 0 scores the in-sample residual
+        against the filtered mean, which is not a prediction error.  horizons and gains as forecast().
+
+        Returns dict(n [K, L] int64, sum_err, sum_sq [K, L] fp64, pvar [K, L] fp64 -- the predictive variance of an observation,
+        forecast_variances() + noise, for h >= 1 -- or None with gains "handle", x [L, d] end state, status [L] int32, horizons: the list).  A
+        latent whose Kalman DARE did not converge has status 1, n = 0 and NaN elsewhere.  Asynchronous on the current torch stream; `x`, `x_start`
+        as forecast().  score_summary() turns the sums into mse, bias, smse and mlpd."""
+        T, ld = self._check_stream(Ty, T)
+        hz, K = _int_list(horizons, "horizon", FORECAST_MAX_HORIZONS)
+        g = _forecast_gains(gains)
+        t_first = _first_origin(t_first, T)
+        self._refuse_stacked("forecast_scores")
+        x, start = self._start_state(Ty, x, x_start)
+        n = torch.empty((K, self.L), dtype=torch.int64, device=Ty.device)
+        sum_err = torch.empty((K, self.L), dtype=torch.float64, device=Ty.device)
+        sum_sq = torch.empty_like(sum_err)
+        pvar = torch.empty_like(sum_err) if g == 0 else None
+        status = torch.empty((self.L,), dtype=torch.int32, device=Ty.device)
+        rc = self._lib.moihgp_forecast_scores(self._h, _DT[Ty.dtype], C.c_void_p(Ty.data_ptr()), T, ld,
+                                              C.c_void_p(start.data_ptr()), C.c_void_p(x.data_ptr()), hz, K, t_first, g,
+                                              C.c_void_p(n.data_ptr()), C.c_void_p(sum_err.data_ptr()), C.c_void_p(sum_sq.data_ptr()),
+                                              C.c_void_p(pvar.data_ptr()) if pvar is not None else None,
+                                              C.c_void_p(status.data_ptr()), _stream_ptr(stream))
+        _check(rc, self._lib)
+        return dict(n=n, sum_err=sum_err, sum_sq=sum_sq, pvar=pvar, x=x, status=status, horizons=[int(h) for h in hz])
+
     def lagged(self, Ty: torch.Tensor, lags, T: Optional[int] = None, x: Optional[torch.Tensor] = None, x_start: Optional[torch.Tensor] = None,
                state_at: Optional[int] = None, out: Optional[torch.Tensor] = None, ypred: Optional[torch.Tensor] = None, stream=None):
         """Fixed-lag smoothing of T ticks for every latent (include/moihgp.h moihgp_lagged_stream): lag[k, l, t] is the mean of latent l at tick t
@@ -705,6 +743,41 @@ def forecast_outputs(gp, Y: torch.Tensor, horizons, tail: int = 0, gains: str = 
     # (with gains "handle" the means exist, but var_Y does not)
     return Yf, _output_variances(gp, var, bad, f"forecast_outputs: the Kalman DARE of {bad} latent(s) did not converge; their rows and variances are NaN "
                                  "and so is every output that mixes them"), Ytail
+
+
+def score_summary(scores: dict) -> dict:
+    """Per (horizon, latent) figures from the sums of LatentBank.forecast_scores / score_outputs: mse = sum_sq / n and bias = sum_err / n; where
+    the dict holds pvar (gains "kalman") also smse = mse / pvar, which is ~ 1 for a calibrated model, and the mean log predictive density
+    mlpd = -1/2 (log(2 pi pvar) + mse / pvar).  smse and mlpd are NaN for h = 0 (in-sample: pvar is not its variance) and wherever n = 0, as are
+    mse and bias there.  At h = 1, -n mlpd is the steady-state Kalman negative log likelihood of the scored ticks.  Torch ops on the sums' own
+    device, no synchronisation."""
+    n = scores["n"].to(torch.float64)
+    nan = torch.full_like(n, float("nan"))
+    some = n > 0
+    den = torch.where(some, n, torch.ones_like(n))
+    out = dict(mse=torch.where(some, scores["sum_sq"] / den, nan), bias=torch.where(some, scores["sum_err"] / den, nan))
+    pvar = scores.get("pvar")
+    if pvar is not None:
+        # (one fill per horizon: a host list copied to the device would wait for the stream)
+        ahead = torch.cat([torch.full((1, 1), bool(h > 0), dtype=torch.bool, device=n.device) for h in scores["horizons"]]) & some
+        out["smse"] = torch.where(ahead, out["mse"] / pvar, nan)
+        out["mlpd"] = torch.where(ahead, -0.5 * (torch.log(2.0 * np.pi * pvar) + out["mse"] / pvar), nan)
+    return out
+
+
+def score_outputs(gp, Y: torch.Tensor, horizons, t_first: int = 0, gains: str = "kalman", stream=None) -> dict:
+    """Forecast scores of a tick-major observation stream Y [T, M] (NaN = missing output) with the parameters of `gp` (a pywrapper.MOIHGP), from
+    a zero state: project_stream -> LatentBank.forecast_scores on the projected streams; returns that method's dict.  Ticks with missing outputs
+    are projected as project_stream does it (forecast_outputs): a tick with more than 64 missing outputs or fewer than L observed ones is missing
+    as a whole, and is then no target.
+
+    The scores are those of the projected streams.  With orthonormal mixing columns and fully observed ticks, the squared forecast error of the
+    outputs inside the mixing's span is sum_l S_l sum_sq[k, l]; that sum is stated here, not computed."""
+    _check_observations(gp, Y)
+    bank = LatentBank.from_handle(gp)
+    Ty = project_stream(gp, Y, stream=stream)
+    with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
+        return bank.forecast_scores(Ty, horizons, T=Y.shape[0], t_first=t_first, gains=gains, stream=stream)
 
 
 def lagged_outputs(gp, Y: torch.Tensor, lags, stream=None):

@@ -4,10 +4,11 @@ Plain run: one line per (dtype, K, cache state) with the event-timed duration of
 status kernel), its algorithmic traffic (1 + K) L T sizeof(scalar) and the share of the 8 TB/s HBM peak that is.  "cold" evicts the caches
 between calls by writing a 2 GB buffer; "resident" repeats the call on the same buffers.
 
---alternate: after a warm-up, `--iters` rounds of [smooth, forecast K=1, forecast K=4] per dtype, for a run under
-`rocprofv3 --kernel-trace --output-format csv`: the parent's smooth_fwd_kernel and the forecast sweep are then timed in the same job, interleaved.
---summarize FILE: per-kernel median / min / max of such a kernel trace, the K = 1 sweep against smooth_fwd_kernel and the K = 4 call against
-four times it."""
+--alternate: after a warm-up, `--iters` rounds of [smooth, forecast K=1, forecast K=many, scores K=1, scores K=many] per dtype (`--many` 4 or 8),
+for a run under `rocprofv3 --kernel-trace --output-format csv`: the parent's smooth_fwd_kernel, the forecast sweep and the scoring sweep
+(moihgp_forecast_scores) are then timed in the same job, interleaved.
+--summarize FILE: per-kernel median / min / max of such a kernel trace, the K = 1 sweep against smooth_fwd_kernel, the K = many call against
+that many times it, and the scoring sweeps against the forecast sweeps of the same K."""
 import argparse
 import csv
 import os
@@ -21,7 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 HBM_PEAK = 8e12
 
 
-def summarize(path):
+def summarize(path, many=4):
     rows = list(csv.DictReader(open(path)))
     dur = {}
     for r in rows:
@@ -47,8 +48,19 @@ def summarize(path):
               f"{k1[0] / fwd[0]:.2f} x  -> {'ok' if k1[0] <= fwd[0] * (1 + spread) else 'SLOWER than smooth_fwd by more than its spread'}")
         if k4:
             small = sum(stat[k][0] for k in stat if k.startswith("forecast_tables_kernel<3") or k.startswith(f"forecast_serial_kernel<{tv}, 3"))
-            print(f"{tv}: forecast K=4 sweep median {k4[0]:.1f} us + tables and status kernels {small:.1f} us = {k4[0] + small:.1f} us vs 4 x smooth_fwd "
-                  f"{4 * fwd[0]:.1f} us -> {'ok' if k4[0] + small < 4 * fwd[0] else 'NOT under four sweeps'}")
+            print(f"{tv}: forecast K={many} sweep median {k4[0]:.1f} us + tables and status kernels {small:.1f} us = {k4[0] + small:.1f} us vs {many} x "
+                  f"smooth_fwd {many * fwd[0]:.1f} us -> {'ok' if k4[0] + small < many * fwd[0] else 'NOT under that many sweeps'}")
+        # the scoring sweeps (forecast_score_kernel<Tv, Ta, D, KG, NG, STAGED>; K = 1 is KG = NG = 1) against the forecast sweep of the same K, with
+        # that kernel's own range as the margin
+        sc = {k: stat[k] for k in stat if k.startswith(f"forecast_score_kernel<{tv}, {tv}, 3, ")}
+        one = [k for k in sc if re.match(rf"forecast_score_kernel<{tv}, {tv}, 3, 1, 1\b", k)]
+        for K, fc, keys in ((1, k1, one), (many, k4, [k for k in sc if k not in one])):
+            if not (fc and keys):
+                continue
+            s = sc[keys[0]]
+            margin = max(fc[2] - fc[0], fc[0] - fc[1])
+            print(f"{tv}: scores K={K} sweep median {s[0]:.1f} us (min {s[1]:.1f}, max {s[2]:.1f}) vs forecast K={K} sweep {fc[0]:.1f} us "
+                  f"(min {fc[1]:.1f}, max {fc[2]:.1f}) = {s[0] / fc[0]:.2f} x  -> {'ok' if s[0] <= fc[0] + margin else 'SLOWER than the forecast sweep by more than its range'}")
 
 
 def main():
@@ -58,11 +70,12 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--gains", default="kalman", choices=["kalman", "handle"])
     ap.add_argument("--path", type=int, default=-1, help='option "forecast_path": -1 automatic, 0 scan kernel, 1 serial fp64')
-    ap.add_argument("--alternate", action="store_true", help="rounds of [smooth, forecast K=1, forecast K=4] for a kernel-trace run")
+    ap.add_argument("--alternate", action="store_true", help="rounds of [smooth, forecast K=1, forecast K=many, scores K=1, scores K=many] for a kernel-trace run")
+    ap.add_argument("--many", type=int, default=4, choices=[4, 8], help="the larger K of --alternate and --summarize")
     ap.add_argument("--summarize", metavar="FILE", help="kernel-trace csv of an --alternate run")
     a = ap.parse_args()
     if a.summarize:
-        return summarize(a.summarize)
+        return summarize(a.summarize, a.many)
     import torch
     from multioutputihgp_amd.streams import LatentBank
     torch.cuda.set_device(0)
@@ -85,7 +98,9 @@ def main():
             for _ in range(a.iters + a.iters // 4 + 1):
                 bank.smooth(Ty, x=x, ysmooth=ys)
                 bank.forecast(Ty, horizons[1], x=x, out=out[:1], gains=a.gains)
-                bank.forecast(Ty, horizons[4], x=x, out=out[:4], gains=a.gains)
+                bank.forecast(Ty, horizons[a.many], x=x, out=out[:a.many], gains=a.gains)
+                bank.forecast_scores(Ty, horizons[1], x=x, gains=a.gains)
+                bank.forecast_scores(Ty, horizons[a.many], x=x, gains=a.gains)
                 torch.cuda.synchronize()
             continue
         for K in (1, 4, 8):
