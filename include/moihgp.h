@@ -371,6 +371,40 @@ int moihgp_lagged_stream(moihgp_gp* gp, int dtype, const void* Ty, size_t T, siz
                          int* status, void* stream);
 int moihgp_lagged_variances(moihgp_gp* gp, const int* lags, size_t K, double* var);
 
+/* ---- off-grid smoothing of whole streams: means between ticks, with variances (not in the reference) -----------------------------------------
+ * The posterior mean of every latent at times BETWEEN the ticks given the whole stream: the smoothed signal upsampled, for resampling, for
+ * alignment with another clock, for plotting.  (Smoothing a NaN-padded stream with a bank at dt / n is n times the work and is not this: the
+ * steady-state gains of that bank assume an observation every dt / n.)
+ * Per latent, take the smoother's tables A, K, G, P, PF, Ps (moihgp_smooth_stream), Pinf and F of the model, H = e0, and its two passes:
+ *     forward    xp[t] = A xf[t-1] (xf[-1] = x_in);  p[t] = H xp[t];  v[t] = y[t] - p[t] (0 where y[t] is NaN);  xf[t] = xp[t] + K v[t]
+ *     backward   s[T] = 0;  s[t] = G s[t+1] + K v[t];  ys[t] = p[t] + s[t]_0
+ * For fractions phi_0 .. phi_{K-1} (finite, 0 <= phi < 1, 1 <= K <= MOIHGP_INTERP_MAX_POINTS, need not be sorted or distinct):
+ *     A_phi = expm(F phi dt);  B_phi = expm(F (1 - phi) dt);  P_phi = A_phi PF A_phi^T + Pinf - A_phi Pinf A_phi^T;  G_phi = P_phi B_phi^T P^-1
+ *     fine[k][l][t] = a_k . xf[t] + g_k . s[t+1],   a_k = H A_phi_k,  g_k = H G_phi_k          0 <= t < T
+ *     var[k][l]     = ( P_phi + G_phi (Ps - P) G_phi^T )_00
+ * i.e. plane k holds at index t the mean of the latent at time (t + phi_k) dt given all T ticks: the RTS smoother with an unobserved point
+ * inserted between ticks t and t + 1 (the predicted covariance at t + 1 through that point is again P, so nothing else changes).  At phi = 0 it
+ * is ys[t] (A_0 = I, G_0 = G); at the last tick s[T] = 0, so the value is the forecast phi dt past the end, H A_phi xf[T-1].  The variance is the
+ * steady-state one of the latent FUNCTION (add R for an observation): var_smoothed at phi = 0.  Missing ticks and the two ends are treated as the
+ * smoother treats them: in the interior of a long gap-free stream the result is the exact GP conditional mean and variance; within a few
+ * correlation lengths of the ends and of missing ticks it is the IHGP approximation.
+ * moihgp_interp_stream: Ty, x_in, ld_in, ld_out, alignment, asynchrony and stream bookkeeping as moihgp_lagged_stream.  fracs: HOST double [K], read
+ *   before the call returns.  ysmooth [L][ld_out] (dtype) is required and receives ys, equal to moihgp_smooth_stream's to rounding; fine holds K
+ *   planes [L][ld_out], plane k starting k * plane_stride elements after fine (plane_stride >= L * ld_out and a multiple of 16 bytes).  fine,
+ *   ysmooth and Ty must be mutually disjoint.  x [L][d] receives the end state (x may alias x_in).  status: DEVICE int [L] or NULL; a latent whose
+ *   Kalman DARE did not converge gets status 1 and NaN in all its K rows, in its row of ysmooth and in x.  T = 0 writes x and status only.  The
+ *   smoother's tables are built on the first such call after a table rewrite, exactly as by a smooth.  Arithmetic is fp64 for both stream types (an
+ *   fp32 stream's v and planes are rounded to fp32 between the two passes, its results are narrowed on store).  Returns 1 (and launches nothing)
+ *   for K or an offset out of range, bad strides or alignment, an overlap; 3 for stacked models.
+ *   Option "interp_path" (moihgp_set_option): -1 automatic (the time-parallel scan kernels; a serial fp64 walk for latents whose G or A - K H A
+ *   fails the smoother's growth bound), 0 scan kernels for every latent, 1 serial fp64 walk for every latent.
+ * moihgp_interp_variances: var [K][L] to a HOST buffer (NaN for a latent whose Kalman DARE did not converge).  Synchronises. */
+#define MOIHGP_INTERP_MAX_POINTS 8
+int moihgp_interp_stream(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x,
+                         const double* fracs, size_t K, void* ysmooth, void* fine, size_t ld_out, size_t plane_stride,
+                         int* status, void* stream);
+int moihgp_interp_variances(moihgp_gp* gp, const double* fracs, size_t K, double* var);
+
 /* ---- seeded steady-state posterior samples of whole streams (not in the reference) -----------------------------------------------------------
  * Joint draws over time of every latent given ALL the ticks of the stream: the smoother's mean plus a stationary deviation process with the
  * steady-state posterior's covariance across time.  The textbook backward sampler (x~[t] = xf[t] + G (x~[t+1] - A xf[t]) + w, w ~ N(0, PF - G P G^T))

@@ -176,6 +176,21 @@ public:
             return rc ? rc : d.fetch(d.buf[2]);
         }, [](size_t l, int) { return "the Kalman DARE of latent " + std::to_string(l) + " did not converge"; })[0];
     }
+    // (not in the reference) Off-grid smoothing of the series with the current parameters (include/moihgp.h moihgp_interp_stream): element t is the
+    // mean of every output at time (t + frac) dt given ALL of Y, from a zero start state -- predictSmoothed(Y) at frac 0; the last element is the
+    // forecast frac dt past the end.  fp64 on the device: project_stream -> interp_stream -> unproject_stream.  Throws std::invalid_argument for a
+    // frac outside [0, 1) (NaN included) and std::runtime_error if a latent's Kalman DARE did not converge (status 1: its row would be NaN).
+    // Missing outputs (NaN) are projected as in predictSmoothed().
+    std::vector<Vector> predictBetween(const std::vector<Vector>& Y, double frac) {
+        if (!(frac >= 0.0 && frac < 1.0)) throw std::invalid_argument("predictBetween: frac must be in [0, 1)");
+        const size_t T = Y.size(), L = _num_latent, ld = (T + 1) / 2 * 2;
+        if (T == 0) return std::vector<Vector>();
+        return streamRoundTrip("predictBetween", Y, {L * ld, L * ld, L * ld}, [&](StreamTrip& d) {
+            int rc = d.project();
+            if (!rc) rc = moihgp_interp_stream(d.h, MOIHGP_F64, d.buf[0], T, ld, d.x, d.x, &frac, 1, d.buf[1], d.buf[2], ld, L * ld, d.status, d.s);
+            return rc ? rc : d.fetch(d.buf[2]);
+        }, [](size_t l, int) { return "the Kalman DARE of latent " + std::to_string(l) + " did not converge"; })[0];
+    }
     // (not in the reference) predict() as ONE pass over the whole series on the device (include/moihgp.h): project -> filter -> un-project in
     // fp64 from a zero start state, where predict() makes one gp32_step3 round trip per tick; element t is what predict() returns at tick t, to
     // rounding.  tiled = true runs the segment-major entries (moihgp_project_stream_tiled -> moihgp_filter_stream_tiled ->

@@ -153,6 +153,9 @@ struct moihgp_gp {
     // fixed-lag smoothing (moihgp_lagged_stream): the per-call tables (fp64 alone), rebuilt by every call for its lags
     CallTables lt;
     int opt_lagged_path = -1;            // option "lagged_path": -1 automatic, 0 scan kernels, 1 serial fp64
+    // off-grid smoothing (moihgp_interp_stream): the per-call tables (fp64 alone), rebuilt by every call for its offsets
+    CallTables itp;
+    int opt_interp_path = -1;            // option "interp_path": -1 automatic, 0 scan kernels, 1 serial fp64
     // posterior sampling (moihgp_sample_stream): the realization's per-latent tables, built lazily behind the smoother's (ensure_sampler)
     LazyTables sp;
     int opt_sample_path = -1;            // option "sample_path": -1 automatic, 0 scan kernel, 1 serial fp64
@@ -162,7 +165,7 @@ struct moihgp_gp {
 
 static void gp_free(moihgp_gp* g) {
     if (!g) return;
-    void* ptrs[] = {g->dU, g->dS, g->dsqrtS, g->dinvsqrtS, g->dsigma, g->dparams, g->cb64, g->cb32, g->dx, g->dpart, g->dTy, g->dUty, g->dTyhat, g->dloss, g->dgrad, g->dscratch, g->dwork, g->dpolar, g->dfallback, g->dwin, g->dunstable, g->dxscratch, g->cbd64, g->dU32, g->dhp, g->dlink, g->dwinmiss, g->dtp64, g->dtp32, g->dxc64, g->dxc32, g->dlinkflags, g->dgap, g->drescue_idx, g->drescue, g->drescue_const, g->sm.d, g->fc.d64, g->fc.d32, g->sp.d, g->lt.d64};
+    void* ptrs[] = {g->dU, g->dS, g->dsqrtS, g->dinvsqrtS, g->dsigma, g->dparams, g->cb64, g->cb32, g->dx, g->dpart, g->dTy, g->dUty, g->dTyhat, g->dloss, g->dgrad, g->dscratch, g->dwork, g->dpolar, g->dfallback, g->dwin, g->dunstable, g->dxscratch, g->cbd64, g->dU32, g->dhp, g->dlink, g->dwinmiss, g->dtp64, g->dtp32, g->dxc64, g->dxc32, g->dlinkflags, g->dgap, g->drescue_idx, g->drescue, g->drescue_const, g->sm.d, g->fc.d64, g->fc.d32, g->sp.d, g->lt.d64, g->itp.d64};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (void* p : g->pinned) (void)hipHostUnregister(p);
@@ -172,7 +175,7 @@ static void gp_free(moihgp_gp* g) {
     if (g->hflag) (void)hipHostFree(g->hflag);
     for (hipEvent_t e : g->prof_ev) (void)hipEventDestroy(e);
     if (g->order_ev) (void)hipEventDestroy(g->order_ev);
-    for (hipEvent_t e : {g->sm.ev, g->fc.ev, g->sp.ev, g->lt.ev})
+    for (hipEvent_t e : {g->sm.ev, g->fc.ev, g->sp.ev, g->lt.ev, g->itp.ev})
         if (e) (void)hipEventDestroy(e);
     if (g->stream) (void)hipStreamDestroy(g->stream);
     delete g;
@@ -1330,6 +1333,57 @@ int moihgp_lagged_variances(moihgp_gp* gp, const int* lags, size_t K, double* va
     return guard_rc([&] { return lagged_variances_impl(gp, lags, K, var); });
 }
 
+// ---- off-grid smoothing (interp.hip) -------------------------------------------------------------------------------------------------------------
+// 1 .. MOIHGP_INTERP_MAX_POINTS finite fractions in [0, 1) into fr, zero padded.
+static int check_frac_list(const double* in, size_t K, InterpFracs& fr) {
+    if (K < 1 || K > (size_t)MOIHGP_INTERP_MAX_POINTS) { set_last_error("interp: the number of offsets (%zu) must be 1 .. %d", K, MOIHGP_INTERP_MAX_POINTS); return 1; }
+    if (!in) { set_last_error("interp: null offsets"); return 1; }
+    for (double& v : fr.f) v = 0.0;
+    for (size_t k = 0; k < K; k++) {
+        if (!std::isfinite(in[k]) || in[k] < 0.0 || !(in[k] < 1.0)) { set_last_error("interp: offset %zu (%g) must be finite and in [0, 1)", k, in[k]); return 1; }
+        fr.f[k] = in[k];
+    }
+    return 0;
+}
+
+// The tables depend on the call's offsets, so every call builds them on its own stream into the handle's buffer, as the fixed-lag smoother does.
+static void build_interp_tables(moihgp_gp* gp, const InterpFracs& fr, size_t K, hipStream_t s) {
+    call_tables_begin(gp, gp->itp, (size_t)it_size(gp->d), false, s);
+    launch_interp_tables(kernel_base(gp->kernel), gp->d, gp->cb64, gp->sm.d, gp->L, gp->dt, fr, (int)K, gp->itp.d64, s);
+}
+
+static int interp_stream_impl(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x, const double* fracs, size_t K,
+                              void* ysmooth, void* fine, size_t ld_out, size_t plane_stride, int* status, void* stream) {
+    if (int rc = check_sweep_call(gp, dtype, Ty, T, ld_in, x_in, x)) return rc;
+    InterpFracs fr;
+    if (int rc = check_frac_list(fracs, K, fr)) return rc;
+    const SweepIo io = stream_sweep_io(gp, dtype, Ty, T, ld_in, x_in, x, ysmooth, ld_out, stream);
+    // the backward sweep reads y, the predicted means and the planes beside the ticks it writes: the three may not overlap
+    if (int rc = check_outputs(io, {{ysmooth, "ysmooth", "ysmooth"}, {fine, "fine buffer", "the fine buffer", K, plane_stride}})) return rc;
+    if (int rc = ensure_smoother(gp, io.stream)) return rc;
+    note_user_stream(gp, io.stream);
+    build_interp_tables(gp, fr, K, io.stream);
+    launch_interp_stream(gp->d, io, gp->sm.d, gp->itp.d64, SweepPlanes{fine, plane_stride, (int)K}, status, gp->opt_interp_path);
+    call_tables_end(gp->itp, io.stream);
+    return 0;
+}
+
+static int interp_variances_impl(moihgp_gp* gp, const double* fracs, size_t K, double* var) {
+    if (!gp) { set_last_error("null handle"); return 1; }
+    InterpFracs fr;
+    if (int rc = check_frac_list(fracs, K, fr)) return rc;
+    return read_call_variances(gp, gp->itp, (size_t)it_size(gp->d), (size_t)(gp->d == 2 ? IT<2>::VAR : IT<3>::VAR), K, var,
+                               [&] { build_interp_tables(gp, fr, K, gp->stream); });
+}
+
+int moihgp_interp_stream(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x, const double* fracs, size_t K,
+                         void* ysmooth, void* fine, size_t ld_out, size_t plane_stride, int* status, void* stream) {
+    return guard_rc([&] { return interp_stream_impl(gp, dtype, Ty, T, ld_in, x_in, x, fracs, K, ysmooth, fine, ld_out, plane_stride, status, stream); });
+}
+int moihgp_interp_variances(moihgp_gp* gp, const double* fracs, size_t K, double* var) {
+    return guard_rc([&] { return interp_variances_impl(gp, fracs, K, var); });
+}
+
 // ---- seeded steady-state posterior sampling (sampler.hip) ---------------------------------------------------------------------------------------
 // The realization's tables follow the smoother's, by the same protocol (ensure_tables).  The rewrites themselves do nothing for them.
 static int ensure_sampler(moihgp_gp* g, hipStream_t s) {
@@ -1716,7 +1770,7 @@ int moihgp_release_stream(moihgp_gp* gp, void* stream) {
             MOIHGP_HIP_FATAL(hipEventRecord(gp->order_ev, s));
             MOIHGP_HIP_FATAL(hipStreamWaitEvent(gp->stream, gp->order_ev, 0));
             gp->user_streams.erase(gp->user_streams.begin() + (long)i);
-            for (CallTables* t : {&gp->fc, &gp->lt})          // (the handle's stream now follows s: a later forecast or fixed-lag call on any other
+            for (CallTables* t : {&gp->fc, &gp->lt, &gp->itp})   // (the handle's stream now follows s: a later forecast, fixed-lag or off-grid call on any other
                 if (t->last == s) t->last = gp->stream;       // stream waits for the tables' event)
             break;
         }
@@ -1736,6 +1790,7 @@ int moihgp_set_option(moihgp_gp* gp, const char* name, long value) {
     if (n == "sample_path") { if (value < -1 || value > 1) { set_last_error("sample_path: -1 (automatic), 0 (scan kernel), 1 (serial fp64)"); return 1; } gp->opt_sample_path = (int)value; return 0; }
     if (n == "smoother_path") { if (value < -1 || value > 1) { set_last_error("smoother_path: -1 (automatic), 0 (scan kernels), 1 (serial fp64)"); return 1; } gp->opt_smoother_path = (int)value; return 0; }
     if (n == "lagged_path") { if (value < -1 || value > 1) { set_last_error("lagged_path: -1 (automatic), 0 (scan kernels), 1 (serial fp64)"); return 1; } gp->opt_lagged_path = (int)value; return 0; }
+    if (n == "interp_path") { if (value < -1 || value > 1) { set_last_error("interp_path: -1 (automatic), 0 (scan kernels), 1 (serial fp64)"); return 1; } gp->opt_interp_path = (int)value; return 0; }
     if (n == "forecast_path") { if (value < -1 || value > 1) { set_last_error("forecast_path: -1 (automatic), 0 (scan kernel), 1 (serial fp64)"); return 1; } gp->opt_forecast_path = (int)value; return 0; }
     if (n == "filter_variant") {
 #ifdef MOIHGP_TUNING

@@ -271,6 +271,14 @@ struct LagList { int lag[kLagMaxLags]; };
 void launch_lagged_tables(int d, const double* sm, size_t L, const LagList& lags, int K, double* lt, hipStream_t stream);
 void launch_lagged_stream(int d, const SweepIo& io, const double* sm, const double* lt, size_t T_state, const LagList& lags, const SweepPlanes& out,
                           int* status, int path);
+// interp.hip: off-grid smoothing (include/moihgp.h moihgp_interp_stream).  Per-latent fp64 block IT<D> of it_size(d) doubles (stream_tables.h), built per
+// call for the call's offsets from the model (cb64, dt) and the smoother's blocks sm, which the sweeps read beside it.  io.yhat (ysmooth) receives the
+// smoothed means on the grid, out the K planes between the ticks; io.x the end state.  path as launch_smooth_stream's.
+constexpr int kInterpMaxPoints = 8;   // MOIHGP_INTERP_MAX_POINTS
+struct InterpFracs { double f[kInterpMaxPoints]; };
+void launch_interp_tables(int kernel, int d, const double* cb64, const double* sm, size_t L, double dt, const InterpFracs& fracs, int K, double* it,
+                          hipStream_t stream);
+void launch_interp_stream(int d, const SweepIo& io, const double* sm, const double* it, const SweepPlanes& out, int* status, int path);
 // sampler.hip: seeded steady-state posterior samples (include/moihgp.h moihgp_sample_stream).  Per-latent fp64 block SP<D> of sp_size(d) doubles
 // (stream_tables.h) from the smoother's blocks sm; io.yhat: the smoothed means the deviations are added to (read; of io, only it, T, L, ld_out and the
 // queue matter here); samples: one plane per sample.  path as launch_smooth_stream's.  status: 0 ok, 1 Kalman DARE failed, 2 realization failed

@@ -1,5 +1,5 @@
 // scan_sweep.h -- device machinery of the chunk-scan sweeps over whole streams (smoother.hip: smooth_fwd_kernel, smooth_bwd_kernel;
-// forecast.hip: forecast_sweep_kernel; sampler.hip: sample_sweep_kernel; lagged.hip: lagged_bwd_kernel).  One wavefront per latent walks the stream in segments of
+// forecast.hip: forecast_sweep_kernel; sampler.hip: sample_sweep_kernel; lagged.hip: lagged_bwd_kernel; interp.hip: interp_fwd_kernel, interp_bwd_kernel).  One wavefront per latent walks the stream in segments of
 // 64 x kScanChunk ticks staged through LDS (coalesced in and out): each lane takes kScanChunk consecutive ticks, computes its chunk's affine map
 // from a zero state, a Kogge-Stone scan of the maps over the 64 lanes gives every lane its true start state, and the lane replays its chunk from
 // there.  Both directions live here: forward in time (chunk_map, lane 0 first) and backward (chunk_response_bwd, lane 63 first, a chunk walked

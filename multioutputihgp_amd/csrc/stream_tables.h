@@ -1,4 +1,4 @@
-// stream_tables.h -- the per-latent table blocks of the whole-stream smoother (smoother.hip), forecasts (forecast.hip), fixed-lag smoother (lagged.hip) and sampler (sampler.hip), the
+// stream_tables.h -- the per-latent table blocks of the whole-stream smoother (smoother.hip), forecasts (forecast.hip), fixed-lag smoother (lagged.hip), off-grid smoother (interp.hip) and sampler (sampler.hip), the
 // chunk geometry their chunk powers are built for, and the (d, dtype) dispatch of their launchers.  Read by those files and by capi.cpp.
 #pragma once
 #include "common.h"
@@ -44,6 +44,17 @@ struct LT {
     static constexpr int SIZE = (STATUS + 1 + 1) / 2 * 2;
 };
 
+// per-latent off-grid block (fp64), offsets in doubles, next to the latent's SM<D> block: per offset phi_k the two rows of
+// fine[k][t] = a_k . xf[t] + g_k . s[t+1] (interp.hip)
+template <int D>
+struct IT {
+    static constexpr int AROW = 0;                                    // [kInterpMaxPoints][D]  a_k = H A_phi_k (rows past the call's K are zero)
+    static constexpr int GROW = AROW + kInterpMaxPoints * D;          // [kInterpMaxPoints][D]  g_k = H G_phi_k
+    static constexpr int VAR = GROW + kInterpMaxPoints * D;           // [kInterpMaxPoints]
+    static constexpr int STATUS = VAR + kInterpMaxPoints;
+    static constexpr int SIZE = (STATUS + 1 + 1) / 2 * 2;
+};
+
 // per-latent sampler block (fp64), offsets in doubles: the innovations realization of the smoother's steady-state autocovariance (sampler.hip),
 // next to the latent's SM<D> block (which holds G, G^kScanChunk and Ps)
 template <int D>
@@ -61,6 +72,7 @@ constexpr int sm_size(int d) { return d == 2 ? SM<2>::SIZE : SM<3>::SIZE; }
 constexpr int fc_size(int d) { return d == 2 ? FT<2>::SIZE : FT<3>::SIZE; }
 constexpr int sp_size(int d) { return d == 2 ? SP<2>::SIZE : SP<3>::SIZE; }
 constexpr int lt_size(int d) { return d == 2 ? LT<2>::SIZE : LT<3>::SIZE; }
+constexpr int it_size(int d) { return d == 2 ? IT<2>::SIZE : IT<3>::SIZE; }
 
 // f(std::integral_constant<int, D>) for the state dimension d (2 or 3); f(Tv(), std::integral_constant<int, D>) for the stream's scalar too
 template <typename F>

@@ -86,6 +86,7 @@ def untile_stream(Tt: torch.Tensor, T: int, out: Optional[torch.Tensor] = None, 
 
 FORECAST_MAX_HORIZONS = 8       # MOIHGP_FORECAST_MAX_HORIZONS
 LAGGED_MAX_LAGS = 8             # MOIHGP_LAGGED_MAX_LAGS
+INTERP_MAX_POINTS = 8           # MOIHGP_INTERP_MAX_POINTS
 _GAINS = {"kalman": 0, "handle": 1}
 
 
@@ -102,6 +103,23 @@ def _int_list(values, noun: str, most: int):
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0 or v > (1 << 20):
             raise ValueError(f"{noun} {v!r} must be an integer in 0 .. 2^20")
     return (C.c_int * len(vs))(*[int(v) for v in vs]), len(vs)
+
+
+def _frac_list(values, most: int = INTERP_MAX_POINTS):
+    """(ctypes double array, K) of an off-grid smoother's offsets: 1 .. INTERP_MAX_POINTS finite numbers in [0, 1), validated as include/moihgp.h
+    states them."""
+    if isinstance(values, (str, bytes)):
+        raise ValueError("fracs must be a sequence of 1 .. 8 numbers in [0, 1)")
+    try:
+        vs = [v for v in values]
+    except TypeError:
+        raise ValueError("fracs must be a sequence of 1 .. 8 numbers in [0, 1)") from None
+    if not 1 <= len(vs) <= most:
+        raise ValueError(f"the number of offsets ({len(vs)}) must be 1 .. {most}")
+    for v in vs:
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or not 0 <= v < 1:
+            raise ValueError(f"offset {v!r} must be a finite number in [0, 1)")
+    return (C.c_double * len(vs))(*[float(v) for v in vs]), len(vs)
 
 
 def _row_stride(name: str, buf: torch.Tensor, T: int, Ty: torch.Tensor, also: str = "") -> int:
@@ -195,7 +213,7 @@ class LatentBank:
 
     def set_option(self, name: str, value: int):
         """Per-handle tuning / test hooks (include/moihgp.h moihgp_set_option): "filter_split" (0 automatic, 1 off, n slices),
-        "filter_maxlinks", "filter_variant" (tuning builds only), "smoother_path", "forecast_path", "sample_path" (-1 automatic, 0 scan kernels, 1 serial fp64)."""
+        "filter_maxlinks", "filter_variant" (tuning builds only), "smoother_path", "forecast_path", "sample_path", "lagged_path", "interp_path" (-1 automatic, 0 scan kernels, 1 serial fp64)."""
         _check(self._lib.moihgp_set_option(self._h, name.encode(), int(value)), self._lib)
 
     def update(self, params_LP):
@@ -536,6 +554,37 @@ class LatentBank:
         _check(self._lib.moihgp_lagged_variances(self._h, lg, K, var.ctypes.data_as(c_double_p)), self._lib)
         return var
 
+    def interpolate(self, Ty: torch.Tensor, fracs, T: Optional[int] = None, x: Optional[torch.Tensor] = None, x_start: Optional[torch.Tensor] = None,
+                    out: Optional[torch.Tensor] = None, ysmooth: Optional[torch.Tensor] = None, stream=None):
+        """Off-grid smoothing of T ticks for every latent (include/moihgp.h moihgp_interp_stream): fine[k, l, t] is the mean of latent l at time
+        (t + fracs[k]) dt given the whole stream, with the smoother's steady-state gains.  fracs: 1 .. 8 finite numbers in [0, 1), in any order;
+        offset 0 is smooth(), and the last column of a plane is the forecast fracs[k] dt past the end; interp_variances() gives the variances.
+
+        Returns (fine [K, L, >=T], ysmooth [L, >=T] the smoothed means on the grid, x [L, d] end state, status [L] int32: 0 ok, 1 Kalman DARE not
+        converged (rows, ysmooth row and x NaN)).  Asynchronous on the current torch stream.  `x`, `x_start` as smooth(); `out` (optional)
+        [K, L, >=T] as forecast()'s, `ysmooth` (optional) as smooth()'s; `out`, `ysmooth` and Ty must not overlap each other."""
+        T, ld = self._check_stream(Ty, T)
+        fr, K = _frac_list(fracs)
+        self._refuse_stacked("interpolate")
+        x, start = self._start_state(Ty, x, x_start)
+        out, ld_out, plane, ysmooth, hand_over = self._plane_and_row_buffers(Ty, T, K, out, ysmooth)
+        status = torch.empty((self.L,), dtype=torch.int32, device=Ty.device)
+        rc = self._lib.moihgp_interp_stream(self._h, _DT[Ty.dtype], C.c_void_p(Ty.data_ptr()), T, ld,
+                                            C.c_void_p(start.data_ptr()), C.c_void_p(x.data_ptr()), fr, K,
+                                            C.c_void_p(ysmooth.data_ptr()), C.c_void_p(out.data_ptr()), ld_out, plane,
+                                            C.c_void_p(status.data_ptr()), _stream_ptr(stream))
+        _check(rc, self._lib)
+        return out, hand_over(stream), x, status
+
+    def interp_variances(self, fracs) -> np.ndarray:
+        """var [K, L] (moihgp_interp_variances), fp64 numpy: the steady-state variance of the latent function at time (t + frac) dt given the whole
+        stream (add the noise parameter for an observation): var_smoothed at offset 0, larger between the ticks; NaN for a latent whose Kalman DARE
+        did not converge."""
+        fr, K = _frac_list(fracs)
+        var = np.zeros((K, self.L))
+        _check(self._lib.moihgp_interp_variances(self._h, fr, K, var.ctypes.data_as(c_double_p)), self._lib)
+        return var
+
     def forecast_tail(self, x: torch.Tensor, n: int, stream=None) -> torch.Tensor:
         """tail[l, j] = H A^(j+1) x_l, 0 <= j < n (moihgp_forecast_tail): the forecast beyond the end of a stream from its end state x [L, d]."""
         n = int(n)
@@ -798,3 +847,43 @@ def lagged_outputs(gp, Y: torch.Tensor, lags, stream=None):
     bad = int(((status != 0).cpu().numpy() | np.isnan(var).any(axis=0)).sum())
     return Yl, _output_variances(gp, var, bad, f"lagged_outputs: the Kalman DARE of {bad} latent(s) did not converge; their rows and variances are NaN "
                                  "and so is every output that mixes them")
+
+
+def interpolate_outputs(gp, Y: torch.Tensor, fracs, stream=None):
+    """Smoothed outputs between the ticks of a tick-major observation stream Y [T, M] (NaN = missing output) with the parameters of `gp` (a
+    pywrapper.MOIHGP), from a zero state: project_stream -> LatentBank.interpolate -> unproject_stream per offset.
+
+    Returns (Yfine [K, T, M] in Y's dtype, Ys [T, M] the smoothed outputs on the grid, var_fine [K, M], var_Y [M] fp64 numpy).  Yfine[k, t] is the
+    mean of the outputs at time (t + fracs[k]) dt given all T ticks (its last row: the forecast fracs[k] dt past the end).  var_fine[k, m] =
+    sum_l U[m, l]^2 S_l var[k, l] and var_Y as smooth_outputs': the steady-state variances of the latent FUNCTION at output m, without the observation
+    noise.  Raises MoihgpError if any latent's Kalman DARE did not converge.  Ticks with missing outputs are projected as project_stream does it:
+    a tick with more than 64 missing outputs or fewer than L observed ones is treated as missing as a whole."""
+    T = Y.shape[0]
+    bank = LatentBank.from_handle(gp)
+    _, K = _frac_list(fracs)
+    Ty = project_stream(gp, Y, stream=stream)
+    fine, ys, _, status = bank.interpolate(Ty, fracs, T=T, stream=stream)
+    Yfine = torch.stack([unproject_stream(gp, fine[k], T, stream=stream) for k in range(K)])
+    Ys = unproject_stream(gp, ys, T, stream=stream)
+    var = bank.interp_variances(fracs)      # (synchronises)
+    bad = int(((status != 0).cpu().numpy() | np.isnan(var).any(axis=0)).sum())
+    message = (f"interpolate_outputs: the Kalman DARE of {bad} latent(s) did not converge; their rows and variances are NaN and so is every output "
+               "that mixes them")
+    var_fine = _output_variances(gp, var, bad, message)
+    return Yfine, Ys, var_fine, _output_variances(gp, bank.latent_variances()[1], bad, message)
+
+
+def upsample_outputs(gp, Y: torch.Tensor, factor: int, stream=None):
+    """The smoothed outputs of Y [T, M] on a grid `factor` times as fine (2 .. 9): interpolate_outputs at the offsets j / factor, interleaved with
+    the smoothed outputs on the grid by torch ops.
+
+    Returns (Yup [(T - 1) factor + 1, M] with Yup[t factor + j] the mean at time (t + j / factor) dt -- the points past the last tick are dropped --
+    and var_up [factor, M] fp64 numpy, the steady-state variance of the latent function at offset j / factor: var_up[0] is smooth_outputs' var_Y)."""
+    if isinstance(factor, bool) or not isinstance(factor, (int, np.integer)) or not 2 <= factor <= INTERP_MAX_POINTS + 1:
+        raise ValueError(f"factor {factor!r} must be an integer in 2 .. {INTERP_MAX_POINTS + 1}")
+    factor = int(factor)
+    T, M = Y.shape[0], Y.shape[1]
+    Yfine, Ys, var_fine, var_Y = interpolate_outputs(gp, Y, [j / factor for j in range(1, factor)], stream=stream)
+    with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
+        Yup = torch.cat([Ys[None], Yfine]).permute(1, 0, 2).reshape(T * factor, M)[:max((T - 1) * factor + 1, 0)]
+    return Yup, np.concatenate([var_Y[None], var_fine])
