@@ -405,6 +405,40 @@ int moihgp_interp_stream(moihgp_gp* gp, int dtype, const void* Ty, size_t T, siz
                          int* status, void* stream);
 int moihgp_interp_variances(moihgp_gp* gp, const double* fracs, size_t K, double* var);
 
+/* ---- slopes of whole streams: the rate of change of every latent, with variances (not in the reference) ----------------------------------------
+ * The derivative with respect to TIME (the unit of dt, not ticks) of the posterior mean of every latent, on or between the ticks, and the posterior
+ * variance of that derivative: for trends, turning points and "is it rising, and are we sure" bands.  (Differencing moihgp_interp_stream's planes
+ * gives a mean but the wrong variance, and none for the real-time case.)
+ * Take A_phi, B_phi, P_phi, G_phi of moihgp_interp_stream above, M_phi = P_phi - Pinf, H = e0, and the smoother's two passes (xf, p, v forward; s
+ * backward).  For offsets phi_0 .. phi_{K-1} (as moihgp_interp_stream's: finite, 0 <= phi < 1, 1 <= K <= MOIHGP_INTERP_MAX_POINTS):
+ *     given all ticks (MOIHGP_SLOPE_ALL):         slope[k][l][t] = a_k . xf[t] + gd_k . s[t+1]
+ *                                                 a_k = e1^T A_phi_k       gd_k = e0^T (F M_phi_k - Pinf F^T) B_phi_k^T P^-1
+ *                                                 var[k][l] = (P_phi_k)_11 + gd_k (Ps - P) gd_k^T
+ *     given the ticks <= t (MOIHGP_SLOPE_PAST):   slope[k][l][t] = a_k . xf[t]          var[k][l] = (P_phi_k)_11
+ * slope[k][l][t] is d/dtau of the posterior mean of latent l at time tau = (t + phi_k) dt.  With ALL it is the derivative with respect to phi dt of
+ * moihgp_interp_stream's plane; with PAST the derivative of the forecast phi dt ahead of tick t, at phi = 0 the real-time slope estimate.
+ * gd = d g_phi / dtau, since d M_phi / dtau = F M_phi + M_phi F^T and d B_phi^T / dtau = -F^T B_phi^T; equivalently
+ *     gd = e1^T G_phi - e0^T (F Pinf + Pinf F^T) B_phi^T P^-1.
+ * The second term vanishes where Pinf solves the Lyapunov equation of F (Matern-3/2).  The reference's Matern-5/2, reproduced literally here, has a
+ * Pinf that does not (row 0 of F Pinf + Pinf F^T has a non-zero entry (0, 2)): there component 1 of the smoothed state is NOT the slope of the
+ * smoothed curve, and the rows e1^T G_phi would be wrong by a third to two thirds of the slope's scale.  The variance is the mixed second derivative,
+ * at phi' = phi, of the smoothed covariance of f between two points of one interval, [P_phi A_(phi'-phi)^T + G_phi (Ps - P) G_phi'^T]_00; its first
+ * term comes to (P_phi)_11 for both models.  The variance is positive and below the prior's Pinf_11.  At the last tick s[T] = 0, so both forms give
+ * the slope of the forecast.  Missing ticks and the two ends are the smoother's steady-state approximation, as everywhere: in the interior of a long
+ * gap-free stream mean and variance are those of the exact GP posterior of f' (given all ticks, or the ticks <= t).
+ * moihgp_slope_stream: every argument and check as moihgp_interp_stream's (offsets, strides, alignment, overlap, asynchrony, status, T = 0, failed
+ *   latents, stacked models rc 3); slope holds the K planes.  given other than the two constants returns 1; a bad call launches nothing.  ysmooth
+ *   [L][ld_out] is required: with MOIHGP_SLOPE_ALL it receives the smoothed means, as moihgp_interp_stream's; with MOIHGP_SLOPE_PAST it is scratch of
+ *   unspecified content (only the forward sweep runs).  The sweeps are moihgp_interp_stream's kernels, so the option "interp_path" governs the
+ *   route here too.  The call's tables live in a buffer of their own: a slope call and an off-grid call on two streams do not wait for each other.
+ * moihgp_slope_variances: var [K][L] to a HOST buffer (NaN for a latent whose Kalman DARE did not converge).  Synchronises. */
+#define MOIHGP_SLOPE_ALL 0
+#define MOIHGP_SLOPE_PAST 1
+int moihgp_slope_stream(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x,
+                        const double* fracs, size_t K, int given, void* ysmooth, void* slope, size_t ld_out, size_t plane_stride,
+                        int* status, void* stream);
+int moihgp_slope_variances(moihgp_gp* gp, const double* fracs, size_t K, int given, double* var);
+
 /* ---- seeded steady-state posterior samples of whole streams (not in the reference) -----------------------------------------------------------
  * Joint draws over time of every latent given ALL the ticks of the stream: the smoother's mean plus a stationary deviation process with the
  * steady-state posterior's covariance across time.  The textbook backward sampler (x~[t] = xf[t] + G (x~[t+1] - A xf[t]) + w, w ~ N(0, PF - G P G^T))

@@ -191,6 +191,21 @@ public:
             return rc ? rc : d.fetch(d.buf[2]);
         }, [](size_t l, int) { return "the Kalman DARE of latent " + std::to_string(l) + " did not converge"; })[0];
     }
+    // (not in the reference) Rate of change of the series with the current parameters (include/moihgp.h moihgp_slope_stream): element t is the
+    // derivative with respect to time (the unit of dt) of the mean of every output at time (t + frac) dt, from a zero start state -- given ALL of Y,
+    // or with past = true given the ticks up to t only (at frac 0 the real-time slope estimate).  fp64 on the device: project_stream ->
+    // slope_stream -> unproject_stream.  Throws as predictBetween does.
+    std::vector<Vector> predictSlope(const std::vector<Vector>& Y, double frac = 0.0, bool past = false) {
+        if (!(frac >= 0.0 && frac < 1.0)) throw std::invalid_argument("predictSlope: frac must be in [0, 1)");
+        const size_t T = Y.size(), L = _num_latent, ld = (T + 1) / 2 * 2;
+        if (T == 0) return std::vector<Vector>();
+        return streamRoundTrip("predictSlope", Y, {L * ld, L * ld, L * ld}, [&](StreamTrip& d) {
+            int rc = d.project();
+            if (!rc) rc = moihgp_slope_stream(d.h, MOIHGP_F64, d.buf[0], T, ld, d.x, d.x, &frac, 1, past ? MOIHGP_SLOPE_PAST : MOIHGP_SLOPE_ALL, d.buf[1],
+                                              d.buf[2], ld, L * ld, d.status, d.s);
+            return rc ? rc : d.fetch(d.buf[2]);
+        }, [](size_t l, int) { return "the Kalman DARE of latent " + std::to_string(l) + " did not converge"; })[0];
+    }
     // (not in the reference) predict() as ONE pass over the whole series on the device (include/moihgp.h): project -> filter -> un-project in
     // fp64 from a zero start state, where predict() makes one gp32_step3 round trip per tick; element t is what predict() returns at tick t, to
     // rounding.  tiled = true runs the segment-major entries (moihgp_project_stream_tiled -> moihgp_filter_stream_tiled ->

@@ -27,6 +27,7 @@ ADDITIVE_SYMBOLS = [
     "moihgp_forecast_stream", "moihgp_forecast_tail", "moihgp_forecast_variances", "moihgp_forecast_scores",
     "moihgp_lagged_stream", "moihgp_lagged_variances",
     "moihgp_interp_stream", "moihgp_interp_variances",
+    "moihgp_slope_stream", "moihgp_slope_variances",
     "moihgp_sample_stream", "moihgp_sample_noise", "moihgp_get_sampler",
     "moihgp_dvec_ctx_new", "moihgp_dvec_ctx_del", "moihgp_dvec_ctx_stream", "moihgp_dvec_alloc", "moihgp_dvec_alloc_mask", "moihgp_dvec_free", "moihgp_dvec_trim", "moihgp_dvec_cache_limit", "moihgp_dvec_upload", "moihgp_dvec_download",
     "moihgp_dvec_copy", "moihgp_dvec_sync", "moihgp_dvec_dot", "moihgp_dvec_axpy", "moihgp_dvec_scale", "moihgp_dvec_sub", "moihgp_dvec_clamp", "moihgp_dvec_active_set",
@@ -183,6 +184,11 @@ def load_library():
                                          C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
     lib.moihgp_interp_variances.restype = C.c_int
     lib.moihgp_interp_variances.argtypes = [C.c_void_p, c_double_p, C.c_size_t, c_double_p]
+    lib.moihgp_slope_stream.restype = C.c_int
+    lib.moihgp_slope_stream.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, c_double_p, C.c_size_t, C.c_int,
+                                        C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
+    lib.moihgp_slope_variances.restype = C.c_int
+    lib.moihgp_slope_variances.argtypes = [C.c_void_p, c_double_p, C.c_size_t, C.c_int, c_double_p]
     lib.moihgp_dvec_ctx_new.restype = C.c_void_p
     lib.moihgp_dvec_ctx_del.restype = None; lib.moihgp_dvec_ctx_del.argtypes = [C.c_void_p]
     lib.moihgp_dvec_sync.restype = C.c_int; lib.moihgp_dvec_sync.argtypes = [C.c_void_p]

@@ -156,6 +156,9 @@ struct moihgp_gp {
     // off-grid smoothing (moihgp_interp_stream): the per-call tables (fp64 alone), rebuilt by every call for its offsets
     CallTables itp;
     int opt_interp_path = -1;            // option "interp_path": -1 automatic, 0 scan kernels, 1 serial fp64
+    // slopes (moihgp_slope_stream): per-call tables of the off-grid smoother's layout, for the call's offsets and `given`; the sweeps and their option are
+    // the off-grid smoother's
+    CallTables slt;
     // posterior sampling (moihgp_sample_stream): the realization's per-latent tables, built lazily behind the smoother's (ensure_sampler)
     LazyTables sp;
     int opt_sample_path = -1;            // option "sample_path": -1 automatic, 0 scan kernel, 1 serial fp64
@@ -165,7 +168,7 @@ struct moihgp_gp {
 
 static void gp_free(moihgp_gp* g) {
     if (!g) return;
-    void* ptrs[] = {g->dU, g->dS, g->dsqrtS, g->dinvsqrtS, g->dsigma, g->dparams, g->cb64, g->cb32, g->dx, g->dpart, g->dTy, g->dUty, g->dTyhat, g->dloss, g->dgrad, g->dscratch, g->dwork, g->dpolar, g->dfallback, g->dwin, g->dunstable, g->dxscratch, g->cbd64, g->dU32, g->dhp, g->dlink, g->dwinmiss, g->dtp64, g->dtp32, g->dxc64, g->dxc32, g->dlinkflags, g->dgap, g->drescue_idx, g->drescue, g->drescue_const, g->sm.d, g->fc.d64, g->fc.d32, g->sp.d, g->lt.d64, g->itp.d64};
+    void* ptrs[] = {g->dU, g->dS, g->dsqrtS, g->dinvsqrtS, g->dsigma, g->dparams, g->cb64, g->cb32, g->dx, g->dpart, g->dTy, g->dUty, g->dTyhat, g->dloss, g->dgrad, g->dscratch, g->dwork, g->dpolar, g->dfallback, g->dwin, g->dunstable, g->dxscratch, g->cbd64, g->dU32, g->dhp, g->dlink, g->dwinmiss, g->dtp64, g->dtp32, g->dxc64, g->dxc32, g->dlinkflags, g->dgap, g->drescue_idx, g->drescue, g->drescue_const, g->sm.d, g->fc.d64, g->fc.d32, g->sp.d, g->lt.d64, g->itp.d64, g->slt.d64};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (void* p : g->pinned) (void)hipHostUnregister(p);
@@ -175,7 +178,7 @@ static void gp_free(moihgp_gp* g) {
     if (g->hflag) (void)hipHostFree(g->hflag);
     for (hipEvent_t e : g->prof_ev) (void)hipEventDestroy(e);
     if (g->order_ev) (void)hipEventDestroy(g->order_ev);
-    for (hipEvent_t e : {g->sm.ev, g->fc.ev, g->sp.ev, g->lt.ev, g->itp.ev})
+    for (hipEvent_t e : {g->sm.ev, g->fc.ev, g->sp.ev, g->lt.ev, g->itp.ev, g->slt.ev})
         if (e) (void)hipEventDestroy(e);
     if (g->stream) (void)hipStreamDestroy(g->stream);
     delete g;
@@ -1384,6 +1387,52 @@ int moihgp_interp_variances(moihgp_gp* gp, const double* fracs, size_t K, double
     return guard_rc([&] { return interp_variances_impl(gp, fracs, K, var); });
 }
 
+// ---- slopes (slope.hip) ------------------------------------------------------------------------------------------------------------------------------
+static int check_given(int given) {
+    if (given != MOIHGP_SLOPE_ALL && given != MOIHGP_SLOPE_PAST) { set_last_error("slope: given (%d) must be MOIHGP_SLOPE_ALL (0) or MOIHGP_SLOPE_PAST (1)", given); return 1; }
+    return 0;
+}
+
+// Per call, as the off-grid smoother's, into a buffer of their own: a slope call and an off-grid call on two streams keep their own tables.
+static void build_slope_tables(moihgp_gp* gp, const InterpFracs& fr, size_t K, int given, hipStream_t s) {
+    call_tables_begin(gp, gp->slt, (size_t)it_size(gp->d), false, s);
+    launch_slope_tables(kernel_base(gp->kernel), gp->d, gp->cb64, gp->sm.d, gp->L, gp->dt, fr, (int)K, given, gp->slt.d64, s);
+}
+
+static int slope_stream_impl(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x, const double* fracs, size_t K,
+                             int given, void* ysmooth, void* slope, size_t ld_out, size_t plane_stride, int* status, void* stream) {
+    if (int rc = check_sweep_call(gp, dtype, Ty, T, ld_in, x_in, x)) return rc;
+    InterpFracs fr;
+    if (int rc = check_frac_list(fracs, K, fr)) return rc;
+    if (int rc = check_given(given)) return rc;
+    const SweepIo io = stream_sweep_io(gp, dtype, Ty, T, ld_in, x_in, x, ysmooth, ld_out, stream);
+    // as the off-grid smoother: y, the predicted means and the planes may not overlap (given the past ysmooth is the forward sweep's scratch row buffer)
+    if (int rc = check_outputs(io, {{ysmooth, "ysmooth", "ysmooth"}, {slope, "slope buffer", "the slope buffer", K, plane_stride}})) return rc;
+    if (int rc = ensure_smoother(gp, io.stream)) return rc;
+    note_user_stream(gp, io.stream);
+    build_slope_tables(gp, fr, K, given, io.stream);
+    launch_slope_stream(gp->d, io, gp->sm.d, gp->slt.d64, SweepPlanes{slope, plane_stride, (int)K}, status, gp->opt_interp_path, given);
+    call_tables_end(gp->slt, io.stream);
+    return 0;
+}
+
+static int slope_variances_impl(moihgp_gp* gp, const double* fracs, size_t K, int given, double* var) {
+    if (!gp) { set_last_error("null handle"); return 1; }
+    InterpFracs fr;
+    if (int rc = check_frac_list(fracs, K, fr)) return rc;
+    if (int rc = check_given(given)) return rc;
+    return read_call_variances(gp, gp->slt, (size_t)it_size(gp->d), (size_t)(gp->d == 2 ? IT<2>::VAR : IT<3>::VAR), K, var,
+                               [&] { build_slope_tables(gp, fr, K, given, gp->stream); });
+}
+
+int moihgp_slope_stream(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, const void* x_in, void* x, const double* fracs, size_t K,
+                        int given, void* ysmooth, void* slope, size_t ld_out, size_t plane_stride, int* status, void* stream) {
+    return guard_rc([&] { return slope_stream_impl(gp, dtype, Ty, T, ld_in, x_in, x, fracs, K, given, ysmooth, slope, ld_out, plane_stride, status, stream); });
+}
+int moihgp_slope_variances(moihgp_gp* gp, const double* fracs, size_t K, int given, double* var) {
+    return guard_rc([&] { return slope_variances_impl(gp, fracs, K, given, var); });
+}
+
 // ---- seeded steady-state posterior sampling (sampler.hip) ---------------------------------------------------------------------------------------
 // The realization's tables follow the smoother's, by the same protocol (ensure_tables).  The rewrites themselves do nothing for them.
 static int ensure_sampler(moihgp_gp* g, hipStream_t s) {
@@ -1770,7 +1819,7 @@ int moihgp_release_stream(moihgp_gp* gp, void* stream) {
             MOIHGP_HIP_FATAL(hipEventRecord(gp->order_ev, s));
             MOIHGP_HIP_FATAL(hipStreamWaitEvent(gp->stream, gp->order_ev, 0));
             gp->user_streams.erase(gp->user_streams.begin() + (long)i);
-            for (CallTables* t : {&gp->fc, &gp->lt, &gp->itp})   // (the handle's stream now follows s: a later forecast, fixed-lag or off-grid call on any other
+            for (CallTables* t : {&gp->fc, &gp->lt, &gp->itp, &gp->slt})   // (the handle's stream now follows s: a later forecast, fixed-lag, off-grid or slope call on any other
                 if (t->last == s) t->last = gp->stream;       // stream waits for the tables' event)
             break;
         }

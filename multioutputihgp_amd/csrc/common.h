@@ -279,6 +279,15 @@ struct InterpFracs { double f[kInterpMaxPoints]; };
 void launch_interp_tables(int kernel, int d, const double* cb64, const double* sm, size_t L, double dt, const InterpFracs& fracs, int K, double* it,
                           hipStream_t stream);
 void launch_interp_stream(int d, const SweepIo& io, const double* sm, const double* it, const SweepPlanes& out, int* status, int path);
+// the forward sweep alone and the status words: plane k receives a_k . xf[t]; io.yhat the predicted means (the smoothed means of a latent walked
+// serially).  For slope.hip, whose rows g_k are zero given the past.
+void launch_interp_forward(int d, const SweepIo& io, const double* sm, const double* it, const SweepPlanes& out, int* status, int path);
+// slope.hip: slopes of whole streams (include/moihgp.h moihgp_slope_stream).  The rows of the rate of change go into an IT<D> block, built per call for
+// the call's offsets and `given` (0 all ticks, 1 the ticks <= t: MOIHGP_SLOPE_ALL / _PAST); the sweeps are interp.hip's, both (given 0) or the forward
+// one alone (given 1, io.yhat is then scratch).  path as launch_interp_stream's.
+void launch_slope_tables(int kernel, int d, const double* cb64, const double* sm, size_t L, double dt, const InterpFracs& fracs, int K, int given,
+                         double* it, hipStream_t stream);
+void launch_slope_stream(int d, const SweepIo& io, const double* sm, const double* it, const SweepPlanes& out, int* status, int path, int given);
 // sampler.hip: seeded steady-state posterior samples (include/moihgp.h moihgp_sample_stream).  Per-latent fp64 block SP<D> of sp_size(d) doubles
 // (stream_tables.h) from the smoother's blocks sm; io.yhat: the smoothed means the deviations are added to (read; of io, only it, T, L, ld_out and the
 // queue matter here); samples: one plane per sample.  path as launch_smooth_stream's.  status: 0 ok, 1 Kalman DARE failed, 2 realization failed

@@ -25,6 +25,8 @@
 //                          v, which leaves as ys = p + s_0.
 //   interp_serial_kernel   one lane per latent, fp64, tick by tick: the latents the scan kernels leave (growth bound failed, option "interp_path" = 1),
 //                          every status word, and the NaN rows of failed latents when it walks all.
+// slope.hip builds other rows into the same IT<D> block and launches these sweeps for them (launch_interp_stream; launch_interp_forward: the
+// forward sweep and the serial kernel alone, for rows g_k = 0).
 // Arithmetic is fp64 for both stream types, as the smoother's; fp32 streams are staged in fp32 (v and the planes are rounded to the stream's own
 // precision) and narrowed on store.
 #include "scan_sweep.h"
@@ -334,30 +336,40 @@ void launch_interp_tables(int kernel, int d, const double* cb64, const double* s
 
 // The call's record and its planes are unpacked here, at the launch lines.
 template <typename Tv, int D, int KG>
-static void launch_scan_kg(const SweepIo& io, const double* sm, const double* it, const SweepPlanes& out, int path) {
+static void launch_scan_kg(const SweepIo& io, const double* sm, const double* it, const SweepPlanes& out, int path, bool backward) {
     const size_t lds = sizeof(Tv) * (size_t)KG * kScanPlane;
     hipLaunchKernelGGL((interp_fwd_kernel<Tv, D, KG>), dim3((unsigned)io.L), dim3(64), lds, io.stream, (const Tv*)io.Ty, io.T, io.ld, sm, it, out.K,
                        (const Tv*)io.xin, (Tv*)io.x, (Tv*)io.yhat, (Tv*)out.base, io.ld_out, out.stride, path);
     MOIHGP_HIP_FATAL(hipGetLastError());
+    if (!backward) return;
     hipLaunchKernelGGL((interp_bwd_kernel<Tv, D, KG>), dim3((unsigned)io.L), dim3(64), lds + sizeof(Tv) * kScanPlane, io.stream, (const Tv*)io.Ty, io.T,
                        io.ld, sm, it, out.K, (Tv*)io.yhat, (Tv*)out.base, io.ld_out, out.stride, path);
     MOIHGP_HIP_FATAL(hipGetLastError());
 }
 
-void launch_interp_stream(int d, const SweepIo& io, const double* sm, const double* it, const SweepPlanes& out, int* status, int path) {
+// backward = false: the forward sweep alone (slope.hip, given the past: the rows g_k of `it` are zero)
+static void launch_sweeps(int d, const SweepIo& io, const double* sm, const double* it, const SweepPlanes& out, int* status, int path, bool backward) {
     if (io.L == 0) return;
     dispatch_stream(d, io.dtype, [&](auto tv, auto dim) {
         using Tv = decltype(tv);
         constexpr int D = decltype(dim)::value;
         if (io.T > 0 && path != 1) {
             // planes staged per replay: one for a single offset, else two (at fp64 26 KB of LDS per wavefront in either sweep, at fp32 17 KB and 13 KB)
-            if (out.K == 1) launch_scan_kg<Tv, D, 1>(io, sm, it, out, path);
-            else launch_scan_kg<Tv, D, 2>(io, sm, it, out, path);
+            if (out.K == 1) launch_scan_kg<Tv, D, 1>(io, sm, it, out, path, backward);
+            else launch_scan_kg<Tv, D, 2>(io, sm, it, out, path, backward);
         }
         hipLaunchKernelGGL((interp_serial_kernel<Tv, D>), dim3((unsigned)((io.L + 63) / 64)), dim3(64), 0, io.stream, (const Tv*)io.Ty, io.T, io.ld, sm, it,
                            io.L, out.K, (const Tv*)io.xin, (Tv*)io.x, (Tv*)io.yhat, (Tv*)out.base, io.ld_out, out.stride, status, io.T > 0 ? path : 1);
     });
     MOIHGP_HIP_FATAL(hipGetLastError());
+}
+
+void launch_interp_stream(int d, const SweepIo& io, const double* sm, const double* it, const SweepPlanes& out, int* status, int path) {
+    launch_sweeps(d, io, sm, it, out, status, path, true);
+}
+
+void launch_interp_forward(int d, const SweepIo& io, const double* sm, const double* it, const SweepPlanes& out, int* status, int path) {
+    launch_sweeps(d, io, sm, it, out, status, path, false);
 }
 
 }  // namespace moihgp

@@ -45,7 +45,7 @@ struct LT {
 };
 
 // per-latent off-grid block (fp64), offsets in doubles, next to the latent's SM<D> block: per offset phi_k the two rows of
-// fine[k][t] = a_k . xf[t] + g_k . s[t+1] (interp.hip)
+// fine[k][t] = a_k . xf[t] + g_k . s[t+1] (interp.hip); slope.hip fills the same block with the rows of the rate of change
 template <int D>
 struct IT {
     static constexpr int AROW = 0;                                    // [kInterpMaxPoints][D]  a_k = H A_phi_k (rows past the call's K are zero)

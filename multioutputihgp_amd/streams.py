@@ -88,6 +88,7 @@ FORECAST_MAX_HORIZONS = 8       # MOIHGP_FORECAST_MAX_HORIZONS
 LAGGED_MAX_LAGS = 8             # MOIHGP_LAGGED_MAX_LAGS
 INTERP_MAX_POINTS = 8           # MOIHGP_INTERP_MAX_POINTS
 _GAINS = {"kalman": 0, "handle": 1}
+_GIVEN = {"all": 0, "past": 1}  # MOIHGP_SLOPE_ALL, MOIHGP_SLOPE_PAST
 
 
 def _int_list(values, noun: str, most: int):
@@ -120,6 +121,13 @@ def _frac_list(values, most: int = INTERP_MAX_POINTS):
         if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or not 0 <= v < 1:
             raise ValueError(f"offset {v!r} must be a finite number in [0, 1)")
     return (C.c_double * len(vs))(*[float(v) for v in vs]), len(vs)
+
+
+def _given_flag(given) -> int:
+    """MOIHGP_SLOPE_ALL / _PAST of a slope call's `given`: "all" or "past", else ValueError."""
+    if not isinstance(given, str) or given not in _GIVEN:
+        raise ValueError(f'given {given!r} must be "all" or "past"')
+    return _GIVEN[given]
 
 
 def _row_stride(name: str, buf: torch.Tensor, T: int, Ty: torch.Tensor, also: str = "") -> int:
@@ -585,6 +593,38 @@ class LatentBank:
         _check(self._lib.moihgp_interp_variances(self._h, fr, K, var.ctypes.data_as(c_double_p)), self._lib)
         return var
 
+    def slope(self, Ty: torch.Tensor, fracs=(0.0,), given: str = "all", T: Optional[int] = None, x: Optional[torch.Tensor] = None,
+              x_start: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, ysmooth: Optional[torch.Tensor] = None, stream=None):
+        """Rate of change of every latent over T ticks (include/moihgp.h moihgp_slope_stream): slope[k, l, t] is the derivative with respect to time
+        (the unit of dt, not ticks) of the posterior mean of latent l at time (t + fracs[k]) dt -- given the whole stream (given = "all": the
+        derivative of interpolate()'s planes) or given the ticks up to t (given = "past": the slope of the forecast fracs[k] dt ahead of tick t, at
+        offset 0 the real-time estimate).  fracs as interpolate()'s; slope_variances() gives the variances.
+
+        Returns (slope [K, L, >=T], ysmooth [L, >=T] the smoothed means on the grid -- None with "past", which runs the forward sweep alone and uses
+        the buffer as scratch --, x [L, d] end state, status [L] int32: 0 ok, 1 Kalman DARE not converged (rows and x NaN)).  Asynchronous on the
+        current torch stream.  `x`, `x_start`, `out`, `ysmooth` as interpolate()'s; the option "interp_path" governs the route."""
+        T, ld = self._check_stream(Ty, T)
+        fr, K = _frac_list(fracs)
+        flag = _given_flag(given)
+        self._refuse_stacked("slope")
+        x, start = self._start_state(Ty, x, x_start)
+        out, ld_out, plane, ysmooth, hand_over = self._plane_and_row_buffers(Ty, T, K, out, ysmooth)
+        status = torch.empty((self.L,), dtype=torch.int32, device=Ty.device)
+        rc = self._lib.moihgp_slope_stream(self._h, _DT[Ty.dtype], C.c_void_p(Ty.data_ptr()), T, ld,
+                                           C.c_void_p(start.data_ptr()), C.c_void_p(x.data_ptr()), fr, K, flag,
+                                           C.c_void_p(ysmooth.data_ptr()), C.c_void_p(out.data_ptr()), ld_out, plane,
+                                           C.c_void_p(status.data_ptr()), _stream_ptr(stream))
+        _check(rc, self._lib)
+        return out, (hand_over(stream) if given == "all" else None), x, status
+
+    def slope_variances(self, fracs=(0.0,), given: str = "all") -> np.ndarray:
+        """var [K, L] (moihgp_slope_variances), fp64 numpy: the steady-state posterior variance of the latent function's time derivative at time
+        (t + frac) dt given the whole stream ("all") or the ticks up to t ("past"); NaN for a latent whose Kalman DARE did not converge."""
+        fr, K = _frac_list(fracs)
+        var = np.zeros((K, self.L))
+        _check(self._lib.moihgp_slope_variances(self._h, fr, K, _given_flag(given), var.ctypes.data_as(c_double_p)), self._lib)
+        return var
+
     def forecast_tail(self, x: torch.Tensor, n: int, stream=None) -> torch.Tensor:
         """tail[l, j] = H A^(j+1) x_l, 0 <= j < n (moihgp_forecast_tail): the forecast beyond the end of a stream from its end state x [L, d]."""
         n = int(n)
@@ -871,6 +911,27 @@ def interpolate_outputs(gp, Y: torch.Tensor, fracs, stream=None):
                "that mixes them")
     var_fine = _output_variances(gp, var, bad, message)
     return Yfine, Ys, var_fine, _output_variances(gp, bank.latent_variances()[1], bad, message)
+
+
+def slope_outputs(gp, Y: torch.Tensor, fracs=(0.0,), given: str = "all", stream=None):
+    """Rate of change of the outputs of a tick-major observation stream Y [T, M] (NaN = missing output) with the parameters of `gp` (a
+    pywrapper.MOIHGP), from a zero state: project_stream -> LatentBank.slope -> unproject_stream per offset (the un-projection is linear, so the
+    planes are the outputs' slopes).
+
+    Returns (dY [K, T, M] in Y's dtype, var_dY [K, M] fp64 numpy).  dY[k, t] is the derivative with respect to time of the mean of the outputs at
+    time (t + fracs[k]) dt given all T ticks (given = "all") or the ticks up to t ("past"); var_dY[k, m] = sum_l U[m, l]^2 S_l var[k, l] its
+    steady-state variance.  Raises MoihgpError if any latent's Kalman DARE did not converge.  Ticks with missing outputs are projected as
+    project_stream does it."""
+    T = Y.shape[0]
+    bank = LatentBank.from_handle(gp)
+    _, K = _frac_list(fracs)
+    Ty = project_stream(gp, Y, stream=stream)
+    slope, _, _, status = bank.slope(Ty, fracs, given, T=T, stream=stream)
+    dY = torch.stack([unproject_stream(gp, slope[k], T, stream=stream) for k in range(K)])
+    var = bank.slope_variances(fracs, given)      # (synchronises)
+    bad = int(((status != 0).cpu().numpy() | np.isnan(var).any(axis=0)).sum())
+    return dY, _output_variances(gp, var, bad, f"slope_outputs: the Kalman DARE of {bad} latent(s) did not converge; their rows and variances are NaN "
+                                 "and so is every output that mixes them")
 
 
 def upsample_outputs(gp, Y: torch.Tensor, factor: int, stream=None):

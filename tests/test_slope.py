@@ -1,0 +1,690 @@
+"""Slopes of whole streams (include/moihgp.h moihgp_slope_stream / _variances): the numpy definition the GPU is held to -- the time derivative of
+the off-grid smoother's mean and that derivative's own variance, pinned against the dense GP posterior of f' on a refined grid, against the rows one
+would write first (component 1 of the smoothed state, wrong for the reference's Matern-5/2) and against differences of test_interp's interp_np (CPU)
+-- then the library's tables and sweeps against it (GPU).
+
+fp32 streams: the bounds come from sweeps_np(..., emulate32=True), which rounds p, v, the planes between the two passes and the results to fp32
+where the kernels stage an fp32 stream.  Its worst row error (conftest.rel_err_rows) against the fp64 reference over every case of test_slope_parity
+(both models, L 1 / 7 / 256, the seven T, both `given`, FRACS1 / FRACS3 / FRACS8), measured on the CPU:
+    planes and end state   FP32_EMU     = 1.71e-6  (Matern-3/2, L = 256, T = 2, "all", offset 3/4; the end state alone 5.9e-8)
+    ysmooth                FP32_EMU_YS  = 2.00e-5  (Matern-3/2, L = 256, T = 1: p + s_0 cancels on a row of one tick; 3.2e-7 and less from T = 16 on)
+test_fp32_emulation_stays_below_its_figures asserts both.  The emulation does not reproduce the order of the device's scans, so the device is
+allowed 8 times each: FP32_TOL = 1.37e-5, FP32_TOL_YS = 1.6e-4.  fp64 streams: 1e-9, as test_interp."""
+import ctypes as C
+import os
+import re
+
+import numpy as np
+import pytest
+import scipy.linalg as sl
+
+from conftest import ROOT, rel_err, rel_err_rows
+from test_forecast import padding_untouched, sentinel_out
+from test_interp import DT, FRACS1, FRACS3, FRACS8, VAR_EDGE, VAR_INNER, F_of, _end_to_end_inputs, interp_np, pool_models, with_gaps
+from test_smoother import KMAP, POOL, bank_and_tables, synth, tables, to_dev
+
+SLOPE_SYMBOLS = ("moihgp_slope_stream", "moihgp_slope_variances")
+GIVEN = ("all", "past")
+FP64_TOL = 1e-9
+FP32_EMU, FP32_EMU_YS = 1.71e-6, 2.00e-5
+FP32_TOL, FP32_TOL_YS = 8 * FP32_EMU, 8 * FP32_EMU_YS
+KERNS = ["Matern32", "Matern52"]
+PARITY_L = [1, 7, 256]
+PARITY_T = [1, 2, 16, 17, 1024, 1025, 2065]
+
+
+def tol_of(dtype, ysmooth=False):
+    return FP64_TOL if dtype == "f64" else (FP32_TOL_YS if ysmooth else FP32_TOL)
+
+
+# ------------------------------------------------------------------------------------------------ numpy definition
+def slope_rows_np(tb, F, dt, phi, given="all"):
+    """(a, gd, var) of one latent and one offset, from the definition."""
+    Ap, Bp = sl.expm(F * (phi * dt)), sl.expm(F * ((1.0 - phi) * dt))
+    Pinf, P = tb["Pinf"], tb["P"]
+    Pp = Ap @ tb["PF"] @ Ap.T + Pinf - Ap @ Pinf @ Ap.T
+    if given == "past":
+        return Ap[1], np.zeros(F.shape[0]), Pp[1, 1]
+    gd = ((F @ (Pp - Pinf) - Pinf @ F.T) @ Bp.T @ np.linalg.inv(P))[0]
+    return Ap[1], gd, Pp[1, 1] + gd @ (tb["Ps"] - P) @ gd
+
+
+def naive_rows_np(tb, F, dt, phi):
+    """The rows one writes first: component 1 of the smoothed state at the inserted point, e1^T A_phi and e1^T G_phi, with the matching "variance"."""
+    Ap, Bp = sl.expm(F * (phi * dt)), sl.expm(F * ((1.0 - phi) * dt))
+    Pp = Ap @ tb["PF"] @ Ap.T + tb["Pinf"] - Ap @ tb["Pinf"] @ Ap.T
+    Gp = Pp @ Bp.T @ np.linalg.inv(tb["P"])
+    return Ap[1], Gp[1], (Pp + Gp @ (tb["Ps"] - tb["P"]) @ Gp.T)[1, 1]
+
+
+def sweeps_np(tbs, a, g, Ty, x_in=None, emulate32=False):
+    """plane[k][l][t] = a[k][l] . xf[t] + g[k][l] . s[t+1] with the smoother's two passes, vectorised over latents; returns (planes, ys, end state).
+    emulate32: p, v, the planes between the two passes and the results are rounded to fp32 where the kernels stage an fp32 stream (the forward
+    pass itself keeps v in fp64; the data are taken to be fp32 numbers already)."""
+    r32 = (lambda z: np.asarray(z, dtype=np.float32).astype(np.float64)) if emulate32 else (lambda z: z)
+    A = np.stack([t["A"] for t in tbs]); K = np.stack([t["K"] for t in tbs]); G = np.stack([t["G"] for t in tbs])
+    L, T = Ty.shape
+    d = A.shape[1]
+    x = np.zeros((L, d)) if x_in is None else np.array(x_in, dtype=np.float64)
+    p = np.zeros((L, T)); q = np.zeros((a.shape[0], L, T))
+    for t in range(T):
+        xp = np.einsum("lij,lj->li", A, x)
+        p[:, t] = xp[:, 0]
+        y = Ty[:, t]
+        x = xp + K * np.where(np.isnan(y), 0.0, y - p[:, t])[:, None]
+        q[:, :, t] = np.einsum("kld,ld->kl", a, x)
+    p, q = r32(p), r32(q)
+    v = r32(np.where(np.isnan(Ty), 0.0, Ty - p))
+    s = np.zeros((L, d)); ys = np.zeros((L, T))
+    for t in range(T - 1, -1, -1):
+        q[:, :, t] += np.einsum("kld,ld->kl", g, s)
+        s = np.einsum("lij,lj->li", G, s) + K * v[:, t:t + 1]
+        ys[:, t] = r32(p[:, t] + r32(s[:, 0]))
+    return r32(q), ys, r32(x)
+
+
+def slope_np(tbs, F_list, dt, fracs, Ty, x_in=None, given="all", emulate32=False):
+    """Returns (slope [K][L][T], ys [L][T], the end state [L][d], var [K][L])."""
+    rows = [[slope_rows_np(tb, F, dt, phi, given) for tb, F in zip(tbs, F_list)] for phi in fracs]
+    a = np.array([[r[0] for r in rk] for rk in rows]); g = np.array([[r[1] for r in rk] for rk in rows])     # [K][L][d]
+    planes, ys, x = sweeps_np(tbs, a, g, Ty, x_in, emulate32)
+    return planes, ys, x, np.array([[r[2] for r in rk] for rk in rows])
+
+
+def dense_slope(tb, F, dt, y, n, ticks, past=False):
+    """Mean and variance of f' on the grid dt / n at the points (t + j / n) dt, t in ticks, 0 <= j < n, given y observed at every n-th point (all of
+    them, or with `past` those up to tick t), under the stationary GP prior with c(tau) = (expm(F |tau|) Pinf)_00, cov(f'(s), f(t)) =
+    sign(s - t) (expm(F |s - t|) Pinf)_10 and prior variance Pinf_11.  Returns (mean [n][len(ticks)], var [n][len(ticks)])."""
+    T = len(y)
+    N = n * T
+    Af = sl.expm(F * (dt / n))
+    c = np.zeros(N); c1 = np.zeros(N); M = np.eye(F.shape[0])
+    for k in range(N):
+        MP = M @ tb["Pinf"]
+        c[k] = MP[0, 0]; c1[k] = MP[1, 0]; M = Af @ M
+    obs = n * np.arange(T)
+    Kd = c[np.abs(obs[:, None] - obs[None, :])] + tb["R"] * np.eye(T)
+    mean = np.zeros((n, len(ticks))); var = np.zeros_like(mean)
+    if not past:
+        Lc = np.linalg.cholesky(Kd)
+        z = sl.solve_triangular(Lc, y, lower=True)
+        for j in range(n):
+            dlt = (n * np.asarray(ticks) + j)[None, :] - obs[:, None]
+            Z = sl.solve_triangular(Lc, np.sign(dlt) * c1[np.abs(dlt)], lower=True)
+            mean[j] = Z.T @ z
+            var[j] = tb["Pinf"][1, 1] - np.sum(Z * Z, axis=0)
+        return mean, var
+    for i, t in enumerate(ticks):
+        Lc = np.linalg.cholesky(Kd[:t + 1, :t + 1])
+        z = sl.solve_triangular(Lc, y[:t + 1], lower=True)
+        for j in range(n):
+            dlt = (n * t + j) - obs[:t + 1]
+            Z = sl.solve_triangular(Lc, np.sign(dlt) * c1[np.abs(dlt)], lower=True)
+            mean[j, i] = Z @ z
+            var[j, i] = tb["Pinf"][1, 1] - Z @ Z
+    return mean, var
+
+
+# ------------------------------------------------------------------------------------------------ CPU
+QUARTERS = [0.0, 0.25, 0.5, 0.75]
+
+
+def _dense_stream():
+    rng = np.random.default_rng(1)
+    T = 400
+    return T, np.sin(0.03 * np.arange(T)) + 0.2 * rng.standard_normal(T)
+
+
+_DENSE = {}
+
+
+def dense_all(kern, prm):
+    """The dense posterior of f' given all ticks on ticks 150 .. 250, computed once per draw (tests 1 and 3 share it)."""
+    key = (kern, prm)
+    if key not in _DENSE:
+        T, y = _dense_stream()
+        _DENSE[key] = dense_slope(tables(kern, DT, prm), F_of(kern, DT, prm), DT, y, 4, np.arange(150, 251))
+    return _DENSE[key]
+
+
+def _dense_errors(kern, prm, given, ticks, mean, dvar, rows_of):
+    """(worst mean error over the mean's scale, worst relative variance error, the variances) of the rows rows_of(tb, F, phi) at QUARTERS."""
+    T, y = _dense_stream()
+    tb, F = tables(kern, DT, prm), F_of(kern, DT, prm)
+    rows = [rows_of(tb, F, phi) for phi in QUARTERS]
+    planes, _, _ = sweeps_np([tb], np.array([[r[0]] for r in rows]), np.array([[r[1]] for r in rows]), y[None, :])
+    var = np.array([r[2] for r in rows])
+    em = max(np.max(np.abs(planes[k, 0, ticks] - mean[k])) / np.max(np.abs(mean[k])) for k in range(4))
+    ev = max(np.max(np.abs(dvar[k] - var[k])) / abs(var[k]) for k in range(4))
+    return em, ev, var
+
+
+@pytest.mark.parametrize("kern", KERNS)
+def test_numpy_all_is_the_gp_posterior_of_the_derivative(kern):
+    """T = 400 ticks observed on every fourth point of a dt / 4 grid, the whole POOL, offsets 0, 1/4, 1/2, 3/4, ticks 150 .. 250: 1e-9 of the mean's
+    scale, 1e-9 relative in the variance (measured 1.3e-12, 1.7e-12), every variance positive and below the prior's Pinf_11."""
+    ticks = np.arange(150, 251)
+    for prm in POOL:
+        mean, dvar = dense_all(kern, prm)
+        em, ev, var = _dense_errors(kern, prm, "all", ticks, mean, dvar, lambda tb, F, phi: slope_rows_np(tb, F, DT, phi, "all"))
+        print(f"{kern} {prm}: mean {em:.1e}, variance {ev:.1e}")
+        assert em <= 1e-9 and ev <= 1e-9, (prm, em, ev)
+        assert np.all(var > 0) and np.all(var < tables(kern, DT, prm)["Pinf"][1, 1]), (prm, var)
+
+
+@pytest.mark.parametrize("kern", KERNS)
+def test_numpy_past_is_the_gp_posterior_given_the_ticks_so_far(kern):
+    """The same against the dense posterior given the ticks <= t only, ticks 150 .. 250 in steps of 10 (measured 7.9e-13, 3.9e-13)."""
+    T, y = _dense_stream()
+    ticks = np.arange(150, 251, 10)
+    for prm in POOL:
+        tb = tables(kern, DT, prm)
+        mean, dvar = dense_slope(tb, F_of(kern, DT, prm), DT, y, 4, ticks, past=True)
+        em, ev, var = _dense_errors(kern, prm, "past", ticks, mean, dvar, lambda tb, F, phi: slope_rows_np(tb, F, DT, phi, "past"))
+        print(f"{kern} {prm}: mean {em:.1e}, variance {ev:.1e}")
+        assert em <= 1e-9 and ev <= 1e-9, (prm, em, ev)
+        assert np.all(var > 0) and np.all(var < tb["Pinf"][1, 1]), (prm, var)
+        assert np.all(var >= np.array([slope_rows_np(tb, F_of(kern, DT, prm), DT, phi, "all")[2] for phi in QUARTERS]))   # more ticks, no less known
+
+
+def test_naive_rows_fail_for_matern52_and_coincide_for_matern32():
+    """Component 1 of the smoothed state is not the slope of the smoothed curve under the reference's Matern-5/2 (its Pinf does not solve the Lyapunov
+    equation of its F): the rows e1^T G_phi miss the dense posterior by more than 0.1 of its scale on every POOL draw (measured 0.33 .. 0.72) where
+    the shipped rows pass at 1e-9; for Matern-3/2 the two sets of rows agree to 1e-12."""
+    ticks = np.arange(150, 251)
+    negative = 0
+    for prm in POOL:
+        tb, F = tables("Matern52", DT, prm), F_of("Matern52", DT, prm)
+        lyap = F @ tb["Pinf"] + tb["Pinf"] @ F.T
+        assert abs(lyap[0, 2]) > 1e-3 * np.max(np.abs(lyap)) and abs(lyap[0, 0]) + abs(lyap[0, 1]) <= 1e-12 * np.max(np.abs(lyap))
+        mean, dvar = dense_all("Matern52", prm)
+        em, _, var = _dense_errors("Matern52", prm, "all", ticks, mean, dvar, lambda tb, F, phi: naive_rows_np(tb, F, DT, phi))
+        good, _, _ = _dense_errors("Matern52", prm, "all", ticks, mean, dvar, lambda tb, F, phi: slope_rows_np(tb, F, DT, phi, "all"))
+        print(f"Matern52 {prm}: naive rows {em:.2f} of the scale, shipped rows {good:.1e}; naive variances {var}")
+        assert em > 0.1 and good <= 1e-9, (prm, em, good)
+        negative += bool(np.any(var < 0))
+    assert negative >= 7          # (7 of the 8 draws: the naive "variance" is not one)
+    for prm in POOL:
+        tb, F = tables("Matern32", DT, prm), F_of("Matern32", DT, prm)
+        assert np.max(np.abs(F @ tb["Pinf"] + tb["Pinf"] @ F.T)[0]) <= 1e-12 * np.max(np.abs(tb["Pinf"]))
+        for phi in QUARTERS:
+            _, g, v = slope_rows_np(tb, F, DT, phi, "all")
+            _, gn, vn = naive_rows_np(tb, F, DT, phi)
+            assert np.max(np.abs(g - gn)) <= 1e-12 * np.max(np.abs(g)) and abs(v - vn) <= 1e-12 * v, (prm, phi)
+
+
+@pytest.mark.parametrize("kern", KERNS)
+def test_numpy_slope_is_the_central_difference_of_the_off_grid_mean(kern):
+    """(interp_np(phi + h) - interp_np(phi - h)) / (2 h dt) at h = 1e-4 against slope_np "all" on a stream with missing ticks and a non-zero start
+    state, offsets 1/4, 1/2, 3/4, every tick (the last, a forecast, included): 1e-6 of the slope's scale (measured 1.2e-8)."""
+    rng = np.random.default_rng(2)
+    T, h = 600, 1e-4
+    y = np.sin(0.03 * np.arange(T)) + 0.2 * rng.standard_normal(T)
+    y[[0, 3, 300, 301, 302, T - 1]] = np.nan
+    for prm in POOL:
+        tb, F = tables(kern, DT, prm), F_of(kern, DT, prm)
+        x0 = 0.1 * rng.standard_normal((1, F.shape[0]))
+        slope, ys, xe, _ = slope_np([tb], [F], DT, QUARTERS[1:], y[None, :], x0)
+        fine, ys2, xe2, _ = interp_np([tb], [F], DT, sum(([phi - h, phi + h] for phi in QUARTERS[1:]), []), y[None, :], x0)
+        assert np.array_equal(ys, ys2) and np.array_equal(xe, xe2)
+        for k in range(3):
+            fd = (fine[2 * k + 1, 0] - fine[2 * k, 0]) / (2 * h * DT)
+            err = np.max(np.abs(fd - slope[k, 0])) / np.max(np.abs(slope[k, 0]))
+            assert err <= 1e-6, (prm, k, err)
+
+
+def test_header_and_loader_declare_the_slope_entries():
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "moihgp.h")).read(), flags=re.S)
+    from multioutputihgp_amd import _lib
+    for n in SLOPE_SYMBOLS:
+        assert re.search(r"\b%s\s*\(" % n, src), n
+        assert n in _lib.ADDITIVE_SYMBOLS, n
+    assert re.search(r"#define\s+MOIHGP_SLOPE_ALL\s+0\b", src) and re.search(r"#define\s+MOIHGP_SLOPE_PAST\s+1\b", src)
+
+
+def test_library_exports_the_slope_entries(hip_built):
+    lib = C.CDLL(hip_built)
+    for n in SLOPE_SYMBOLS:
+        assert hasattr(lib, n), n
+
+
+def _cxx_slope(hip_built):
+    import subprocess
+    build = os.path.join(ROOT, "build", "cxx_tests")
+    os.makedirs(build, exist_ok=True)
+    exe = os.path.join(build, "slope_test")
+    libdir = os.path.dirname(hip_built)
+    subprocess.run(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cxx", "slope_test.cpp"),
+                    "-o", exe, "-L", libdir, "-lmoihgp", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"], check=True)
+    return exe
+
+
+def test_cxx_predict_slope_compiles_and_links(hip_built):
+    assert os.path.exists(_cxx_slope(hip_built))
+
+
+def test_python_argument_validation():
+    from multioutputihgp_amd import streams
+    for ok in ([0], [0.999], np.array([0.25, 0.5]), [0.0] * 8, (0.0,)):
+        arr, K = streams._frac_list(ok)
+        assert K == len(ok) and list(arr) == [float(v) for v in ok]
+    for bad in ([], [0.1] * 9, [1.0], [-0.1], [float("nan")], [float("inf")], "0.5", ["0.5"], [True], 0.5):
+        with pytest.raises(ValueError):
+            streams._frac_list(bad)
+    assert streams._given_flag("all") == 0 and streams._given_flag("past") == 1
+    for bad in ("future", "ALL", "", None, 0, 1, True, b"all", ["all"]):
+        with pytest.raises(ValueError):
+            streams._given_flag(bad)
+
+
+# ------------------------------------------------------------------------------------------------ parity cases (CPU reference, GPU runs)
+_CASES = {}
+
+
+def frac_sets(L):
+    return [("1", FRACS1), ("3", FRACS3)] + ([("8", FRACS8)] if L == 7 else [])
+
+
+def parity_case(kern, L, T):
+    """Stream, start state, numpy reference (both `given`) and its fp32 emulation of one parity case, shared by the dtypes (the data are fp32
+    numbers) and kept unchanged."""
+    key = (kern, L, T)
+    if key not in _CASES:
+        rng = np.random.default_rng(L * 100003 + T)
+        tbs, Fs = pool_models(kern, L)
+        Ty = synth(L, T, rng)
+        if T >= 16:
+            Ty = with_gaps(Ty, rng)
+        Ty = Ty.astype(np.float32).astype(np.float64)
+        x0 = (0.1 * rng.standard_normal((L, Fs[0].shape[0]))).astype(np.float32).astype(np.float64)
+        sets = frac_sets(L)
+        fracs = sum((f for _, f in sets), [])
+        case = dict(Ty=Ty, x0=x0, sets=sets)
+        for given in GIVEN:
+            rows = [[slope_rows_np(tb, F, DT, phi, given) for tb, F in zip(tbs, Fs)] for phi in fracs]
+            a = np.array([[r[0] for r in rk] for rk in rows]); g = np.array([[r[1] for r in rk] for rk in rows])
+            planes, ys, xe = sweeps_np(tbs, a, g, Ty, x0)
+            emu, ys32, xe32 = sweeps_np(tbs, a, g, Ty, x0, emulate32=True)
+            ref, ref32, k = {}, {}, 0
+            for name, f in sets:
+                ref[name] = planes[k:k + len(f)]; ref32[name] = emu[k:k + len(f)]; k += len(f)
+            case[given] = dict(ref=ref, emu=ref32, ys=ys, xe=xe, ys32=ys32, xe32=xe32)
+        _CASES[key] = case
+    return _CASES[key]
+
+
+def emulation_error(case):
+    """Worst row errors of the fp32 emulation of one case against its fp64 reference: (planes of both `given` and end state, ysmooth)."""
+    worst = 0.0
+    for given in GIVEN:
+        c = case[given]
+        for name, fracs in case["sets"]:
+            worst = max([worst] + [rel_err_rows(c["emu"][name][k], c["ref"][name][k]) for k in range(len(fracs))])
+        worst = max(worst, rel_err_rows(c["xe32"], c["xe"], floor=1e-3))
+    return worst, rel_err_rows(case["all"]["ys32"], case["all"]["ys"])
+
+
+def test_fp32_emulation_stays_below_its_figures():
+    """The two figures the fp32 bounds are 8 times of, over the parity cases: all of them up to T = 17 (where both worst cases lie), the long ones
+    with L <= 7 and the longest with L = 256 (measured once over the long L = 256 cases left out here: 3.2e-7 and less)."""
+    errs = [emulation_error(parity_case(kern, L, T)) for kern in KERNS for L in PARITY_L for T in PARITY_T if T <= 17 or L <= 7 or T == 2065]
+    planes, ys = max(e[0] for e in errs), max(e[1] for e in errs)
+    print(f"fp32 emulation: planes and end state {planes:.3e} (FP32_EMU {FP32_EMU:.3e}), ysmooth {ys:.3e} (FP32_EMU_YS {FP32_EMU_YS:.3e})")
+    assert 0.9 * FP32_EMU <= planes <= FP32_EMU and 0.9 * FP32_EMU_YS <= ys <= FP32_EMU_YS
+
+
+# ------------------------------------------------------------------------------------------------ GPU
+@pytest.fixture(scope="module")
+def env(hip_built):
+    import torch
+    assert torch.cuda.is_available(), "GPU suite needs a GPU"
+    torch.cuda.set_device(0)
+    from multioutputihgp_amd import streams
+    return dict(torch=torch, streams=streams)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kern", KERNS)
+@pytest.mark.parametrize("L", PARITY_L)
+@pytest.mark.parametrize("T", PARITY_T)
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+@pytest.mark.parametrize("given", GIVEN)
+def test_slope_parity(env, kern, L, T, dtype, given):
+    """One tick, a chunk and one past it, a segment and one past it, two segments and a ragged third; one, three and (L = 7) eight offsets; a
+    non-zero start state; `out` and `ysmooth` on other row strides than the stream's; missing ticks at the ends and on both sides of the edges."""
+    torch, streams = env["torch"], env["streams"]
+    tdt = torch.float64 if dtype == "f64" else torch.float32
+    case = parity_case(kern, L, T)
+    want = case[given]
+    bank, _, _ = bank_and_tables(streams, kern, L)
+    dev = to_dev(torch, case["Ty"], tdt, T)
+    x_start = torch.from_numpy(case["x0"]).to(tdt).cuda()
+    for name, fracs in case["sets"]:
+        K = len(fracs)
+        slab, out = sentinel_out(torch, K, L, T, tdt)                # ld_out != ld_in, plane_stride > L * ld_out
+        ldo = out.stride(1)
+        yslab = torch.full((L * ldo + 16,), 12345.0, dtype=tdt, device="cuda")
+        ysm = torch.as_strided(yslab, (L, T), (ldo, 1), 0)
+        x = torch.empty_like(x_start)
+        slope, ys, x, status = bank.slope(dev, fracs, given, x=x, x_start=x_start, out=out, ysmooth=ysm)
+        torch.cuda.synchronize()
+        assert int(status.abs().sum()) == 0
+        got = slope.double().cpu().numpy()
+        errs = [rel_err_rows(got[k], want["ref"][name][k]) for k in range(K)]
+        ex = rel_err_rows(x.double().cpu().numpy(), want["xe"], floor=1e-3)
+        print(f"{kern} {dtype} {given} L={L} T={T} fracs={fracs}: planes {['%.1e' % e for e in errs]}, end state {ex:.1e}")
+        assert max(errs) <= tol_of(dtype), errs
+        assert ex <= tol_of(dtype), ex
+        if given == "all":
+            ey = rel_err_rows(ys.double().cpu().numpy(), want["ys"])
+            assert ey <= tol_of(dtype, ysmooth=True), ey
+            assert ys.data_ptr() == ysm.data_ptr()
+        else:
+            assert ys is None
+        assert padding_untouched(torch, slab, out) and padding_untouched(torch, yslab, ysm)
+        assert slope.data_ptr() == out.data_ptr()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+def test_all_runs_the_off_grid_smoothers_sweeps(env, dtype):
+    """With "all" the sweeps are interpolate's on other rows: ysmooth and the end state are bit-equal to interpolate's on the same stream."""
+    torch, streams = env["torch"], env["streams"]
+    tdt = torch.float64 if dtype == "f64" else torch.float32
+    L, T = 7, 2065
+    case = parity_case("Matern52", L, T)
+    bank, _, _ = bank_and_tables(streams, "Matern52", L)
+    dev = to_dev(torch, case["Ty"], tdt, T)
+    x_start = torch.from_numpy(case["x0"]).to(tdt).cuda()
+    for fracs in (FRACS1, FRACS3):
+        _, ys, x, _ = bank.slope(dev, fracs, "all", x_start=x_start)
+        _, yi, xi, _ = bank.interpolate(dev, fracs, x_start=x_start)
+        torch.cuda.synchronize()
+        assert torch.equal(ys, yi) and torch.equal(x, xi)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kern", KERNS)
+def test_slope_is_the_central_difference_of_interpolate_on_the_device(env, kern):
+    """(interpolate(1/2 + h) - interpolate(1/2 - h)) / (2 h dt), h = 1e-3, in fp64 on the device against slope(1/2).  The bound is what the
+    same difference costs in numpy on the same case (truncation h^2 dt^2 f''' / 6 and numpy's own rounding, measured here per row) plus the
+    difference of two planes each good to FP64_TOL of its row's scale, divided by 2 h dt."""
+    torch, streams = env["torch"], env["streams"]
+    L, T, h = 7, 1025, 1e-3
+    case = parity_case(kern, L, T)
+    tbs, Fs = pool_models(kern, L)
+    bank, _, _ = bank_and_tables(streams, kern, L)
+    fine_np = interp_np(tbs, Fs, DT, [0.5 - h, 0.5 + h], case["Ty"], case["x0"])[0]
+    ref = case["all"]["ref"]["1"][0]
+    scale = np.max(np.abs(ref), axis=1)
+    fd_np = (fine_np[1] - fine_np[0]) / (2 * h * DT)
+    e_np = np.max(np.abs(fd_np - ref), axis=1) / scale
+    dev = to_dev(torch, case["Ty"], torch.float64, T)
+    x_start = torch.from_numpy(case["x0"]).cuda()
+    fine, _, _, _ = bank.interpolate(dev, [0.5 - h, 0.5 + h], x_start=x_start)
+    slope, _, _, _ = bank.slope(dev, [0.5], "all", x_start=x_start)
+    fd = ((fine[1] - fine[0]) / (2 * h * DT)).cpu().numpy()
+    err = np.max(np.abs(fd - slope[0].cpu().numpy()), axis=1) / scale
+    bound = e_np + FP64_TOL + 2 * FP64_TOL * np.max(np.abs(fine_np[0]), axis=1) / (2 * h * DT) / scale
+    print(f"{kern}: numpy difference {e_np.max():.1e}, device difference {err.max():.1e}, bound {bound.min():.1e} .. {bound.max():.1e}")
+    assert np.all(e_np <= 1e-6)
+    assert np.all(err <= bound), (err, bound)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kern", KERNS)
+@pytest.mark.parametrize("given", GIVEN)
+@pytest.mark.parametrize("dtype", ["f64", "f32"])
+def test_scan_and_serial_paths_agree(env, kern, given, dtype):
+    """Option "interp_path" governs the route of the slopes: 0 (scan kernels) and 1 (serial fp64) against numpy and each other at the parity bounds."""
+    torch, streams = env["torch"], env["streams"]
+    tdt = torch.float64 if dtype == "f64" else torch.float32
+    L, T = 7, 2065
+    case = parity_case(kern, L, T)
+    bank, _, _ = bank_and_tables(streams, kern, L)
+    dev = to_dev(torch, case["Ty"], tdt, T)
+    x_start = torch.from_numpy(case["x0"]).to(tdt).cuda()
+    res = []
+    for path in (0, 1):
+        bank.set_option("interp_path", path)
+        s, _, x, st = bank.slope(dev, FRACS3, given, x_start=x_start)
+        torch.cuda.synchronize()
+        assert not st.cpu().numpy().any()
+        res.append((s.double().cpu().numpy(), x.double().cpu().numpy()))
+    ref = case[given]["ref"]["3"]
+    for k in range(3):
+        assert rel_err_rows(res[0][0][k], res[1][0][k]) <= tol_of(dtype)
+        for path in (0, 1):
+            assert rel_err_rows(res[path][0][k], ref[k]) <= tol_of(dtype)
+    assert rel_err_rows(res[0][1], res[1][1], floor=1e-3) <= tol_of(dtype)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kern", KERNS)
+def test_variances_match_numpy(env, kern):
+    """1e-10 relative over the POOL at VAR_INNER; beside the ticks (VAR_EDGE) test_interp's rounding bound of a variance that goes through P^-1,
+    eps cond(P) P_11 / var here.  "past" is (P_phi)_11, which goes through no solve: 1e-10 at every offset."""
+    torch, streams = env["torch"], env["streams"]
+    L = len(POOL)
+    bank, tbs, _ = bank_and_tables(streams, kern, L)
+    _, Fs = pool_models(kern, L)
+    fracs = VAR_INNER + VAR_EDGE
+    var, past = bank.slope_variances(fracs, "all"), bank.slope_variances(fracs, "past")
+    assert var.shape == (8, L) and past.shape == (8, L)
+    eps = np.finfo(np.float64).eps
+    for k, phi in enumerate(fracs):
+        for l in range(L):
+            ref = slope_rows_np(tbs[l], Fs[l], DT, phi, "all")[2]
+            err = abs(var[k, l] - ref) / ref
+            tol = 1e-10 if phi in VAR_INNER else max(1e-10, float(eps * np.linalg.cond(tbs[l]["P"]) * tbs[l]["P"][1, 1] / ref))
+            rp = slope_rows_np(tbs[l], Fs[l], DT, phi, "past")[2]
+            ep = abs(past[k, l] - rp) / rp
+            print(f"{kern} offset {phi} draw {POOL[l]}: all {err:.1e} (bound {tol:.1e}), past {ep:.1e}")
+            assert err <= tol, (phi, l, var[k, l], ref)
+            assert ep <= 1e-10, (phi, l, past[k, l], rp)
+    assert np.all(var > 0) and np.all(var <= past * (1 + 1e-9))
+    assert np.all(past < np.array([tb["Pinf"][1, 1] for tb in tbs])[None, :])
+    assert np.array_equal(bank.slope_variances(), bank.slope_variances([0.0], "all"))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("path", [-1, 0, 1])
+@pytest.mark.parametrize("given", GIVEN)
+def test_failed_latent_gives_nan_rows_and_status_1(env, path, given):
+    """A latent whose DARE cannot converge (NaN magnitude): status 1, NaN rows, end state and variances; the other latents are untouched."""
+    torch, streams = env["torch"], env["streams"]
+    rng = np.random.default_rng(12)
+    L, T, bad = 7, 2500, 3
+    bank, tbs, prm = bank_and_tables(streams, "Matern52", L)
+    _, Fs = pool_models("Matern52", L)
+    prm[bad, 0] = np.nan
+    bank.update(prm)
+    bank.set_option("interp_path", path)
+    Ty = synth(L, T, rng)
+    slope, ys, x, status = bank.slope(to_dev(torch, Ty, torch.float64, T), FRACS3, given)
+    torch.cuda.synchronize()
+    st, got, xg = status.cpu().numpy(), slope.cpu().numpy(), x.cpu().numpy()
+    var = bank.slope_variances(FRACS3, given)
+    assert st[bad] == 1 and np.all(np.isnan(got[:, bad])) and np.all(np.isnan(xg[bad])) and np.all(np.isnan(var[:, bad]))
+    keep = [l for l in range(L) if l != bad]
+    assert not st[keep].any() and np.all(np.isfinite(var[:, keep]))
+    ref, yref, xref, _ = slope_np([tbs[l] for l in keep], [Fs[l] for l in keep], DT, FRACS3, Ty[keep], given=given)
+    for k in range(3):
+        assert rel_err_rows(got[k][keep], ref[k]) <= FP64_TOL
+    assert rel_err_rows(xg[keep], xref, floor=1e-3) <= FP64_TOL
+    if given == "all":
+        gy = ys.cpu().numpy()
+        assert np.all(np.isnan(gy[bad])) and rel_err_rows(gy[keep], yref) <= FP64_TOL
+
+
+@pytest.mark.gpu
+def test_stacked_model_returns_3(env):
+    torch, streams = env["torch"], env["streams"]
+    from multioutputihgp_amd import MoihgpError
+    bank = streams.LatentBank(0.1, np.tile([1.0, 1.0, 1.0, 2.0, 0.1], (4, 1)), kernel="Matern32x2")
+    lib = bank._lib
+    Ty = torch.zeros((4, 64), dtype=torch.float64, device="cuda")
+    x = torch.zeros((4, bank.d), dtype=torch.float64, device="cuda")
+    out, ysm = torch.zeros_like(Ty), torch.zeros_like(Ty)
+    fr = (C.c_double * 1)(0.5)
+    var = np.zeros(4)
+    for given in (0, 1):
+        rc = lib.moihgp_slope_stream(bank._h, 0, C.c_void_p(Ty.data_ptr()), 64, 64, C.c_void_p(x.data_ptr()), C.c_void_p(x.data_ptr()), fr, 1, given,
+                                     C.c_void_p(ysm.data_ptr()), C.c_void_p(out.data_ptr()), 64, 4 * 64, None, None)
+        assert rc == 3
+        assert lib.moihgp_slope_variances(bank._h, fr, 1, given, var.ctypes.data_as(C.POINTER(C.c_double))) == 3
+    with pytest.raises(MoihgpError):
+        bank.slope(Ty, [0.5])
+
+
+@pytest.mark.gpu
+def test_bad_calls_launch_nothing(env):
+    """rc 1 from the C entry for a bad count, offset or `given`, with the buffers left as they were; T = 0 writes the end state and the status words;
+    an `out` over the input stream is refused."""
+    torch, streams = env["torch"], env["streams"]
+    from multioutputihgp_amd import MoihgpError
+    L, T = 4, 64
+    bank, _, _ = bank_and_tables(streams, "Matern52", L)
+    lib = bank._lib
+    Ty = torch.zeros((L, T), dtype=torch.float64, device="cuda")
+    x = torch.full((L, bank.d), 7.0, dtype=torch.float64, device="cuda")
+    out, ysm = torch.full_like(Ty, 7.0), torch.full_like(Ty, 7.0)
+    var = np.full((9, L), 7.0)
+
+    def call(fr, K, given):
+        return lib.moihgp_slope_stream(bank._h, 0, C.c_void_p(Ty.data_ptr()), T, T, C.c_void_p(x.data_ptr()), C.c_void_p(x.data_ptr()),
+                                       (C.c_double * len(fr))(*fr), K, given, C.c_void_p(ysm.data_ptr()), C.c_void_p(out.data_ptr()), T, L * T, None, None)
+    for fr, K, given in (([0.5], 0, 0), ([0.1] * 9, 9, 0), ([1.0], 1, 0), ([-0.1], 1, 1), ([float("nan")], 1, 0), ([float("inf")], 1, 1), ([0.5], 1, 2),
+                         ([0.5], 1, -1)):
+        assert call(fr, K, given) == 1, (fr, K, given)
+        assert lib.moihgp_slope_variances(bank._h, (C.c_double * len(fr))(*fr), K, given, var.ctypes.data_as(C.POINTER(C.c_double))) == 1
+    torch.cuda.synchronize()
+    assert bool((out == 7.0).all()) and bool((ysm == 7.0).all()) and bool((x == 7.0).all()) and np.all(var == 7.0)
+    x0 = torch.full((L, bank.d), 0.25, dtype=torch.float64, device="cuda")
+    for given in GIVEN:
+        _, _, xe, status = bank.slope(Ty, [0.5], given, T=0, x_start=x0)
+        torch.cuda.synchronize()
+        assert torch.equal(xe, x0) and int(status.abs().sum()) == 0
+    with pytest.raises(ValueError, match="must not overlap"):
+        bank.slope(Ty, [0.5], out=Ty[None])
+    both = torch.zeros((2, L, T), dtype=torch.float64, device="cuda")
+    for given in GIVEN:
+        with pytest.raises(MoihgpError, match="must not overlap"):
+            bank.slope(Ty, [0.5], given, out=both[:1], ysmooth=both[0])
+    with pytest.raises(ValueError, match="given"):
+        bank.slope(Ty, [0.5], "future")
+    with pytest.raises(ValueError, match="given"):
+        bank.slope_variances([0.5], 1)
+
+
+@pytest.mark.gpu
+def test_calls_on_two_streams_keep_their_own_tables(env):
+    """A call on a second stream right after one on the first, with other offsets and the other `given`: the second rewrites the handle's per-call
+    tables only after the first has finished with them (the tables' event), so all match their references; an off-grid call in between has tables
+    of its own."""
+    torch, streams = env["torch"], env["streams"]
+    L, T = 256, 2065
+    case = parity_case("Matern52", L, T)
+    bank, tbs, _ = bank_and_tables(streams, "Matern52", L)
+    _, Fs = pool_models("Matern52", L)
+    ref8 = slope_np(tbs, Fs, DT, FRACS8, case["Ty"], case["x0"])[0]
+    fine3 = interp_np(tbs, Fs, DT, FRACS3, case["Ty"], case["x0"])[0]
+    dev = to_dev(torch, case["Ty"], torch.float64, T)
+    x_start = torch.from_numpy(case["x0"]).cuda()
+    torch.cuda.synchronize()
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    a = bank.slope(dev, FRACS8, "all", x_start=x_start, stream=s1)
+    b = bank.slope(dev, FRACS3, "past", x_start=x_start, stream=s2)
+    i = bank.interpolate(dev, FRACS3, x_start=x_start, stream=s1)
+    c = bank.slope(dev, FRACS8, "all", x_start=x_start, stream=s2)
+    torch.cuda.synchronize()
+    for k in range(8):
+        assert rel_err_rows(a[0][k].cpu().numpy(), ref8[k]) <= FP64_TOL
+        assert torch.equal(a[0][k], c[0][k])
+    for k in range(3):
+        assert rel_err_rows(b[0][k].cpu().numpy(), case["past"]["ref"]["3"][k]) <= FP64_TOL
+        assert rel_err_rows(i[0][k].cpu().numpy(), fine3[k]) <= FP64_TOL
+
+
+def _slope_outputs_np(gp, Y, kern, fracs, given):
+    M, L = gp.num_output, gp.num_latent
+    prm = gp.params
+    U, S = prm[:M * L].reshape(M, L), prm[M * L:M * L + L]
+    igp = prm[-3 * L:].reshape(L, 3)
+    Ty = np.zeros((L, Y.shape[0]))
+    for t, y in enumerate(Y):
+        obs = ~np.isnan(y)
+        if obs.sum() < L:
+            Ty[:, t] = np.nan
+            continue
+        U0 = U[obs]
+        Ty[:, t] = np.linalg.solve(U0.T @ U0, U0.T @ y[obs]) / np.sqrt(S)
+    tbs = [tables(kern, DT, igp[l]) for l in range(L)]
+    slope, _, _, var = slope_np(tbs, [F_of(kern, DT, igp[l]) for l in range(L)], DT, fracs, Ty, given=given)
+    return np.einsum("ml,klt->ktm", U * np.sqrt(S), slope), (S[None, :] * var) @ (U ** 2).T
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kern", KERNS)
+@pytest.mark.parametrize("missing", [False, True])
+@pytest.mark.parametrize("given", GIVEN)
+def test_slope_outputs_end_to_end(env, kern, missing, given):
+    torch, streams = env["torch"], env["streams"]
+    from multioutputihgp_amd import MOIHGP
+    rng = np.random.default_rng(27)
+    M, L, T, fracs = 12, 4, 600, [0.0, 0.5]
+    params, Y = _end_to_end_inputs(rng, M, L, T, missing)
+    gp = MOIHGP(DT, M, L, kernel=KMAP[kern])
+    gp.update(params)
+    dY, var_dY = streams.slope_outputs(gp, torch.from_numpy(Y).cuda(), fracs, given)
+    torch.cuda.synchronize()
+    ref, vref = _slope_outputs_np(gp, Y, kern, fracs, given)
+    assert tuple(dY.shape) == (2, T, M) and var_dY.shape == (2, M)
+    for k in range(2):
+        assert rel_err(dY[k].cpu().numpy(), ref[k]) <= 1e-8, (k, rel_err(dY[k].cpu().numpy(), ref[k]))
+    assert rel_err(var_dY, vref) <= 1e-8
+    d0, v0 = streams.slope_outputs(gp, torch.from_numpy(Y).cuda())                 # the defaults: offset 0, given all ticks
+    if given == "all":
+        assert torch.equal(d0[0], dY[0]) and rel_err(v0[0], var_dY[0]) <= 1e-14      # (the products over the latents: one row or two at a time)
+
+
+@pytest.mark.gpu
+def test_slope_outputs_raises_on_a_failed_latent(env):
+    torch, streams = env["torch"], env["streams"]
+    from multioutputihgp_amd import MOIHGP, MoihgpError
+    rng = np.random.default_rng(14)
+    M, L, T = 8, 3, 100
+    gp = MOIHGP(DT, M, L, kernel="Matern52ss")
+    igp = np.column_stack([rng.uniform(0.5, 2, L), rng.uniform(0.5, 2, L), rng.uniform(0.05, 0.2, L)])
+    igp[1, 0] = np.nan
+    gp.update(np.concatenate([(np.eye(M, L) + 0.2 * rng.standard_normal((M, L))).ravel(), rng.uniform(0.5, 2, L), [0.05], igp.ravel()]))
+    for given in GIVEN:
+        with pytest.raises(MoihgpError, match="did not converge"):
+            streams.slope_outputs(gp, torch.from_numpy(rng.standard_normal((T, M))).cuda(), [0.5], given)
+
+
+# ------------------------------------------------------------------------------------------------ C++ (predictSlope)
+@pytest.mark.gpu
+@pytest.mark.parametrize("kern", KERNS)
+def test_cxx_predict_slope_matches_python(env, hip_built, kern):
+    import subprocess
+    torch, streams = env["torch"], env["streams"]
+    from multioutputihgp_amd import MOIHGP
+    rng = np.random.default_rng(28)
+    M, L, T, frac = 12, 4, 300, 0.375
+    params, Y = _end_to_end_inputs(rng, M, L, T, True)
+    fmt = lambda a: " ".join("nan" if np.isnan(v) else repr(float(v)) for v in np.ravel(a))
+    exe = _cxx_slope(hip_built)
+
+    def run(fr, past):
+        inp = f"{0 if kern == 'Matern32' else 1} {M} {L} 0.1 {fr!r} {past} {T}\n{fmt(params)}\n" + "\n".join(fmt(y) for y in Y) + "\n"
+        return subprocess.run([exe], input=inp, capture_output=True, text=True, check=True).stdout.strip().split("\n")
+    gp = MOIHGP(DT, M, L, kernel=KMAP[kern])
+    gp.update(params)
+    for past, given in ((0, "all"), (1, "past")):
+        got = np.array([[float(v) for v in line.split()] for line in run(frac, past)])
+        dY, _ = streams.slope_outputs(gp, torch.from_numpy(Y).cuda(), [frac], given)
+        torch.cuda.synchronize()
+        assert got.shape == (T, M)
+        assert rel_err(got, dY[0].cpu().numpy()) <= 1e-9
+    assert run(1.0, 0) == ["invalid_argument"] and run(-0.25, 1) == ["invalid_argument"]
