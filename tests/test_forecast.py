@@ -11,72 +11,19 @@ import re
 import numpy as np
 import pytest
 
-from conftest import ROOT, rel_err, rel_err_rows
+from conftest import rel_err, rel_err_rows
 from oracle.moihgp_numpy import IHGP
-from test_smoother import CASES, KMAP, POOL, synth, tables, to_dev
+from parity_support import synth
+from stream_reference import forecast_np, forecast_var_np, gain_tables, tables
+from stream_support import (CASES, FP32_TOL, FP64_TIGHT, HMAX, KMAP, POOL, assert_declared, assert_exported, cxx_fmt, cxx_rows, cxx_run,
+                            cxx_test_binary, end_to_end_inputs, env, make_bank, padding_untouched, plane_err, sentinel_out, to_dev,
+                            tol_of)  # noqa: F401  (env: the module's fixture)
 
 FORECAST_SYMBOLS = ("moihgp_forecast_stream", "moihgp_forecast_tail", "moihgp_forecast_variances")
-FP64_TIGHT = 1e-9     # the project's own tolerances (tests/test_gpu_parity.py)
-FP32_TOL = 1e-3
-HMAX = 1 << 20
 HORIZONS = [1, 0, 7, 7, 300, HMAX]      # unsorted, repeated, extreme
 
 
-# ------------------------------------------------------------------------------------------------ numpy definition
-def gain_tables(kern, dt, prm, gains):
-    """A, K, M of include/moihgp.h: "kalman" from the smoother's numpy tables (plus Pinf, PF for the variances), "handle" from the numpy
-    oracle's IHGP.update (the reference's literal DARE)."""
-    if gains == "kalman":
-        tb = tables(kern, dt, prm)
-        assert tb is not None, prm
-        return dict(A=tb["A"], K=tb["K"], M=tb["A"] - np.outer(tb["K"], tb["A"][0]), Pinf=tb["Pinf"], PF=tb["PF"], R=tb["R"])
-    g = IHGP(dt, kern)
-    g.update(np.asarray(prm, dtype=np.float64))
-    return dict(A=g.A, K=g.K[:, 0], M=g.AKHA)
-
-
-def states_np(tbs, Ty, x_in=None):
-    """x[t] = M x[t-1] + K y[t], or A x[t-1] where y[t] is NaN, vectorised over latents: [L][T][d]."""
-    A = np.stack([t["A"] for t in tbs]); K = np.stack([t["K"] for t in tbs]); M = np.stack([t["M"] for t in tbs])
-    L, T = Ty.shape
-    d = A.shape[1]
-    x = np.zeros((L, d)) if x_in is None else np.array(x_in, dtype=np.float64)
-    xs = np.zeros((L, T, d))
-    with np.errstate(over="ignore", invalid="ignore"):
-        for t in range(T):
-            y = Ty[:, t]
-            miss = np.isnan(y)
-            xo = np.einsum("lij,lj->li", M, x) + K * np.where(miss, 0.0, y)[:, None]
-            xm = np.einsum("lij,lj->li", A, x)
-            x = np.where(miss[:, None], xm, xo)
-            xs[:, t] = x
-    return xs
-
-
-def forecast_np(tbs, Ty, horizons, x_in=None):
-    """fc[k][l][t] = H A^h_k x_l[t]; also the end state and each latent's scale max_t |H x_l[t]| (the h = 0 row the errors are taken against)."""
-    xs = states_np(tbs, Ty, x_in)
-    L, T, d = xs.shape
-    c = np.array([[np.linalg.matrix_power(t["A"], int(h))[0] for t in tbs] for h in horizons])          # [K][L][d]
-    with np.errstate(over="ignore", invalid="ignore"):
-        fc = np.einsum("kld,ltd->klt", c, xs)
-    xe = xs[:, -1] if T else (np.zeros((L, d)) if x_in is None else np.array(x_in, dtype=np.float64))
-    scale = np.max(np.abs(xs[:, :, 0]), axis=1) if T else np.ones(L)
-    return fc, xe, scale
-
-
-def forecast_var_np(tb, h):
-    Ah = np.linalg.matrix_power(tb["A"], int(h))
-    return (tb["Pinf"] - Ah @ (tb["Pinf"] - tb["PF"]) @ Ah.T)[0, 0]
-
-
-def plane_err(got, ref, scale, floor=1e-6):
-    """Worst row of max|got - ref| over the latent's h = 0 scale: forecasts decay with h, so a row is not normalised by its own size."""
-    den = np.maximum(scale, floor * max(float(np.max(scale)), 1e-300))
-    with np.errstate(invalid="ignore"):
-        return float(np.max(np.max(np.abs(got - ref), axis=-1) / den))
-
-
+# ------------------------------------------------------------------------------------------------ cross-check of the numpy definition
 def dense_predictive(tb, y, t0, h):
     """Mean and variance of the latent function at tick t0 + h given y[0..t0] under the stationary GP prior with covariance (A^k Pinf)_00."""
     A, Pinf, R = tb["A"], tb["Pinf"], tb["R"]
@@ -92,18 +39,12 @@ def dense_predictive(tb, y, t0, h):
 
 # ------------------------------------------------------------------------------------------------ CPU
 def test_header_and_loader_declare_the_forecast_entries():
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "moihgp.h")).read(), flags=re.S)
-    from multioutputihgp_amd import _lib
-    for n in FORECAST_SYMBOLS:
-        assert re.search(r"\b%s\s*\(" % n, src), n
-        assert n in _lib.ADDITIVE_SYMBOLS, n
+    src = assert_declared(FORECAST_SYMBOLS)
     assert re.search(r"#define\s+MOIHGP_FORECAST_MAX_HORIZONS\s+8\b", src)
 
 
 def test_library_exports_the_forecast_entries(hip_built):
-    lib = C.CDLL(hip_built)
-    for n in FORECAST_SYMBOLS:
-        assert hasattr(lib, n), n
+    assert_exported(hip_built, FORECAST_SYMBOLS)
 
 
 @pytest.mark.parametrize("kern", ["Matern32", "Matern52"])
@@ -193,39 +134,6 @@ def test_python_argument_validation():
 
 
 # ------------------------------------------------------------------------------------------------ GPU
-@pytest.fixture(scope="module")
-def env(hip_built):
-    import torch
-    assert torch.cuda.is_available(), "GPU suite needs a GPU"
-    torch.cuda.set_device(0)
-    from multioutputihgp_amd import streams
-    return dict(torch=torch, streams=streams)
-
-
-def make_bank(streams, kern, L, gains, dt=0.1, pool=POOL):
-    prm = np.array([pool[l % len(pool)] for l in range(L)], dtype=np.float64)
-    tbs = {p: gain_tables(kern, dt, p, gains) for p in pool}
-    return streams.LatentBank(dt, prm, kernel=KMAP[kern]), [tbs[pool[l % len(pool)]] for l in range(L)], prm
-
-
-def sentinel_out(torch, K, L, T, tdt, pad_row=8, pad_plane=12):
-    """[K, L, T] view with ld_out = T rounded up + pad_row and plane_stride = L * ld_out + pad_plane inside a slab filled with a sentinel."""
-    ldo = (T + 3) // 4 * 4 + pad_row
-    plane = L * ldo + pad_plane
-    slab = torch.full((K * plane + 16,), 12345.0, dtype=tdt, device="cuda")
-    return slab, torch.as_strided(slab, (K, L, T), (plane, ldo, 1), 0)
-
-
-def padding_untouched(torch, slab, view):
-    mask = torch.ones_like(slab, dtype=torch.bool)
-    torch.as_strided(mask, view.shape, view.stride(), 0).fill_(False)
-    return bool((slab[mask] == 12345.0).all())
-
-
-def tol_of(dtype):
-    return FP64_TIGHT if dtype == "f64" else FP32_TOL
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("gains", ["kalman", "handle"])
 @pytest.mark.parametrize("kern", ["Matern32", "Matern52"])
@@ -627,37 +535,21 @@ def test_full_size_c3_fp32_sampled(env):
 
 
 # ------------------------------------------------------------------------------------------------ C++ (predictAhead)
-def _cxx_forecast(hip_built):
-    import subprocess
-    build = os.path.join(ROOT, "build", "cxx_tests")
-    os.makedirs(build, exist_ok=True)
-    exe = os.path.join(build, "forecast_test")
-    libdir = os.path.dirname(hip_built)
-    subprocess.run(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cxx", "forecast_test.cpp"),
-                    "-o", exe, "-L", libdir, "-lmoihgp", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    return exe
-
-
 def test_cxx_predict_ahead_compiles_and_links(hip_built):
-    assert os.path.exists(_cxx_forecast(hip_built))
+    assert os.path.exists(cxx_test_binary(hip_built, "forecast_test"))
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("kern", ["Matern32", "Matern52"])
 def test_cxx_predict_ahead_matches_python(env, hip_built, kern):
-    import subprocess
     torch, streams = env["torch"], env["streams"]
     from multioutputihgp_amd import MOIHGP
     rng = np.random.default_rng(34)
     M, L, T, h = 12, 4, 300, 6
-    params = np.concatenate([(np.eye(M, L) + 0.2 * rng.standard_normal((M, L))).ravel(), rng.uniform(0.5, 2, L), [0.05],
-                             np.column_stack([rng.uniform(0.5, 2, L), rng.uniform(0.5, 2, L), rng.uniform(0.05, 0.2, L)]).ravel()])
-    Y = np.sin(0.02 * np.arange(T)[:, None] * (1 + np.arange(M)[None, :] % 5)) + 0.1 * rng.standard_normal((T, M))
-    Y[rng.random((T, M)) < 0.02] = np.nan
-    fmt = lambda a: " ".join("nan" if np.isnan(v) else repr(float(v)) for v in np.ravel(a))
-    inp = f"{0 if kern == 'Matern32' else 1} {M} {L} 0.1 {h} {T}\n{fmt(params)}\n" + "\n".join(fmt(y) for y in Y) + "\n"
-    out = subprocess.run([_cxx_forecast(hip_built)], input=inp, capture_output=True, text=True, check=True).stdout.strip().split("\n")
-    got = np.array([[float(v) for v in line.split()] for line in out])
+    params, Y = end_to_end_inputs(rng, M, L, T, True)
+    inp = f"{0 if kern == 'Matern32' else 1} {M} {L} 0.1 {h} {T}\n{cxx_fmt(params)}\n" + "\n".join(cxx_fmt(y) for y in Y) + "\n"
+    out = cxx_run(cxx_test_binary(hip_built, "forecast_test"), inp)
+    got = cxx_rows(out)
     gp = MOIHGP(0.1, M, L, kernel=KMAP[kern])
     gp.update(params)
     Yf, _, _ = streams.forecast_outputs(gp, torch.from_numpy(Y).cuda(), [h])

@@ -1,5 +1,5 @@
 """Forecast scores (include/moihgp.h moihgp_forecast_scores): backtest error sums per latent and horizon.  The numpy definition is scores_np below
-on top of test_forecast.py's forecast_np; the CPU tests tie it to the textbook Kalman filter's innovations and to draws from the model's own
+on top of stream_reference's forecast_np; the CPU tests tie it to the textbook Kalman filter's innovations and to draws from the model's own
 prior, the GPU tests hold the library's kernels, Python surface and C entry to it.
 
 Bounds of the GPU tests, from the project's own plane bounds (tau = 1e-9 for fp64 streams, 1e-3 for fp32; sc the latent's h = 0 scale of
@@ -19,11 +19,10 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, rel_err_rows
-from test_forecast import FP32_TOL, FP64_TIGHT, forecast_np, forecast_var_np, gain_tables, make_bank
-from test_smoother import KMAP, POOL, smooth_np, synth, tables
+from parity_support import synth
+from stream_reference import forecast_np, forecast_var_np, gain_tables, smooth_np, tables
+from stream_support import FP64_TIGHT, HMAX, POOL, env, gaps_ends_run_copy, make_bank, tdt_of, to_dev_poison, tol_of  # noqa: F401  (env: the module's fixture)
 
-HMAX = 1 << 20
-POISON = 1e30
 HORIZONS = [1, 0, 15, 16, 17, 1023, 1024, HMAX]     # chunk (16) and segment (1024) crossings, h >= T, K = 8
 
 
@@ -172,44 +171,8 @@ def test_scores_are_calibrated_on_draws_from_the_prior(kern):
 
 
 # ------------------------------------------------------------------------------------------------ GPU
-@pytest.fixture(scope="module")
-def env(hip_built):
-    import torch
-    assert torch.cuda.is_available(), "GPU suite needs a GPU"
-    torch.cuda.set_device(0)
-    from multioutputihgp_amd import streams
-    return dict(torch=torch, streams=streams)
-
-
-def to_dev_poison(torch, a, dtype, T):
-    """[L, T] view of a slab filled with a finite poison: the row padding and a whole row past the last latent hold 1e30."""
-    L = a.shape[0]
-    buf = torch.full((L + 1, (T + 3) // 4 * 4 + 4), POISON, dtype=dtype, device="cuda")
-    buf[:L, :T] = torch.from_numpy(a).to(dtype)
-    return buf[:L, :T]
-
-
 def round_to(a, dtype):
     return a.astype(np.float32).astype(np.float64) if dtype == "f32" else a
-
-
-def tol_of(dtype):
-    return FP64_TIGHT if dtype == "f64" else FP32_TOL
-
-
-def tdt_of(torch, dtype):
-    return torch.float64 if dtype == "f64" else torch.float32
-
-
-def with_gaps(Ty, rng):
-    """NaNs at tick 0, at T-1, in a run of 20 (where the stream holds one) and at 1 % scattered."""
-    L, T = Ty.shape
-    Ty = Ty.copy()
-    Ty[:, 0] = np.nan; Ty[:, T - 1] = np.nan
-    if T >= 63:
-        Ty[::2, T // 3:T // 3 + 20] = np.nan
-    Ty[rng.random((L, T)) < 0.01] = np.nan
-    return Ty
 
 
 def assert_scores(got, ref, scale, tau, what=""):
@@ -244,7 +207,7 @@ def test_scores_parity(env, kern, L, T, dtype, gains):
     # (a stream of one tick with its tick missing scores nothing: the short streams also run whole)
     for gaps in ((True, False) if T < 63 else (True,)):
         Ty = synth(L, T, rng)
-        Ty = round_to(with_gaps(Ty, rng) if gaps else Ty, dtype)
+        Ty = round_to(gaps_ends_run_copy(Ty, rng) if gaps else Ty, dtype)
         fc, xref, scale = forecast_np(tbs, Ty, HORIZONS, x0)
         ref = scores_np(fc, Ty, HORIZONS, 0)
         got = bank.forecast_scores(to_dev_poison(torch, Ty, tdt, T), HORIZONS, x_start=x_start, gains=gains)
@@ -294,7 +257,7 @@ def test_horizon_groups(env, kern, dtype):
     rng = np.random.default_rng(51)
     L, T = 9, 1025
     bank, tbs, _ = make_bank(streams, kern, L, "kalman")
-    Ty = round_to(with_gaps(synth(L, T, rng), rng), dtype)
+    Ty = round_to(gaps_ends_run_copy(synth(L, T, rng), rng), dtype)
     dev = to_dev_poison(torch, Ty, tdt, T)
     hs = [17, 1, 1024, 5, 0]
     single = {}
@@ -325,7 +288,7 @@ def test_t_first(env, dtype):
     rng = np.random.default_rng(52)
     L, T, hs = 9, 2050, [1, 0, 16, 1024]
     bank, tbs, _ = make_bank(streams, "Matern52", L, "kalman")
-    Ty = round_to(with_gaps(synth(L, T, rng), rng), dtype)
+    Ty = round_to(gaps_ends_run_copy(synth(L, T, rng), rng), dtype)
     dev = to_dev_poison(torch, Ty, tdt, T)
     fc, xref, scale = forecast_np(tbs, Ty, hs)
     for t_first in (0, 5, 16, 1024, T - 1, T):
@@ -385,7 +348,7 @@ def test_scan_and_serial_paths_agree(env, kern, dtype, gains):
     rng = np.random.default_rng(54)
     L, T, hs = 9, 2050, [0, 1, 7, 300, 1024]
     bank, tbs, _ = make_bank(streams, kern, L, gains)
-    Ty = round_to(with_gaps(synth(L, T, rng), rng), dtype)
+    Ty = round_to(gaps_ends_run_copy(synth(L, T, rng), rng), dtype)
     dev = to_dev_poison(torch, Ty, tdt, T)
     fc, xref, scale = forecast_np(tbs, Ty, hs)
     ref = scores_np(fc, Ty, hs, 3)
@@ -489,7 +452,7 @@ def test_two_calls_give_the_same_bits(env, dtype):
     rng = np.random.default_rng(57)
     L, T = 70, 2050
     bank, _, _ = make_bank(streams, "Matern52", L, "kalman")
-    dev = to_dev_poison(torch, with_gaps(synth(L, T, rng), rng), tdt, T)
+    dev = to_dev_poison(torch, gaps_ends_run_copy(synth(L, T, rng), rng), tdt, T)
     a = bank.forecast_scores(dev, HORIZONS, t_first=9)
     b = bank.forecast_scores(dev, HORIZONS, t_first=9)
     torch.cuda.synchronize()

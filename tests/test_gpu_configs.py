@@ -13,6 +13,7 @@ import pytest
 import torch
 
 from conftest import rel_err, rel_err_rows
+from parity_support import synth_params
 
 pytestmark = pytest.mark.gpu
 SEED = 20260101
@@ -27,10 +28,6 @@ def env(hip_built):
     from oracle import cref
     assert load_library().moihgp_device_count() >= 1
     return dict(MOIHGP=MOIHGP, streams=streams, cref=cref)
-
-
-def synth_params(L, rng):
-    return np.column_stack([rng.uniform(0.5, 2, L), rng.uniform(0.5, 2, L), rng.uniform(0.05, 0.2, L)])
 
 
 # ------------------------------------------------------------------------------------------ C1

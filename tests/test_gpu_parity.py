@@ -10,47 +10,9 @@ import pytest
 import torch
 
 from conftest import load_golden, rel_err, rel_err_rows
+from parity_support import FP32_TOL, FP64_TIGHT, FP64_TOL, KMAP, STACKED, env, synth, synth_params, synth_params_stacked, to_dev  # noqa: F401  (env: fixture)
 
 pytestmark = pytest.mark.gpu
-
-FP64_TOL = 1e-6      # the bar
-FP64_TIGHT = 1e-9    # what we actually expect from fp64 (rounding-order differences only)
-FP32_TOL = 1e-3
-KMAP = {"Matern32": "Matern32", "Matern52": "Matern52ss"}   # oracle kernel -> product kernel name
-
-
-@pytest.fixture(scope="module")
-def env(hip_built):
-    assert torch.cuda.is_available(), "GPU suite needs a GPU"
-    torch.cuda.set_device(0)
-    from multioutputihgp_amd import MOIHGP, load_library
-    from multioutputihgp_amd import streams
-    from oracle import cref
-    lib = load_library()
-    assert lib.moihgp_device_count() >= 1
-    return dict(MOIHGP=MOIHGP, streams=streams, cref=cref, lib=lib)
-
-
-def synth(L, T, rng, nan_frac=0.0):
-    t = np.arange(T)[None, :]; l = np.arange(L)[:, None]
-    Ty = np.sin(0.05 * t * (1 + l % 7)) + 0.1 * rng.standard_normal((L, T))
-    if nan_frac:
-        Ty[rng.random((L, T)) < nan_frac] = np.nan
-    return Ty
-
-
-def synth_params(L, rng):
-    return np.column_stack([rng.uniform(0.5, 2, L), rng.uniform(0.5, 2, L), rng.uniform(0.05, 0.2, L)])
-
-
-def to_dev(a, dtype):
-    """numpy [L, T] -> cuda [L, ld] padded per the alignment contract."""
-    from multioutputihgp_amd.streams import alloc_stream
-    L, T = a.shape
-    t = alloc_stream(L, T, dtype)
-    t.zero_()
-    t[:, :T] = torch.from_numpy(a).to(dtype)
-    return t
 
 
 # ------------------------------------------------------------------------------------------ A7
@@ -783,16 +745,6 @@ def test_unstable_latents_take_the_sequential_path(env, dtype, T, split, monkeyp
 
 
 # ------------------------------------------------------------------------------------------ stacked (sum-of-Matern) latents
-STACKED = ["Matern32x2", "Matern52x2", "Matern52x3", "Matern52x4", "Matern32x4", "Matern32x3"]
-
-
-def synth_params_stacked(L, J, rng):
-    cols = []
-    for _ in range(J):
-        cols += [rng.uniform(0.5, 2, L), rng.uniform(0.5, 2, L)]
-    return np.column_stack(cols + [rng.uniform(0.05, 0.2, L)])
-
-
 @pytest.mark.parametrize("kern", ["Matern32x2", "Matern52x2", "Matern52x3", "Matern52x4"])
 def test_stacked_vs_golden(env, kern):
     g = load_golden(f"stacked_{kern}.npz")

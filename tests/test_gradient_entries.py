@@ -93,14 +93,12 @@ import numpy as np
 import pytest
 
 from conftest import rel_err, rel_err_rows
+from parity_support import FP32_TOL, FP64_TIGHT, KMAP, STACKED, synth, synth_params, synth_params_stacked
+from stream_support import round32
 
-FP64_TIGHT = 1e-9
-FP32_TOL = 1e-3
 CALM = 1e3
 HIDDEN = 1e-2                                            # an entry below this share of its case's largest is invisible to the old fp32 bar
 DT = 0.1
-KMAP = {"Matern32": "Matern32", "Matern52": "Matern52ss"}
-STACKED = ("Matern32x2", "Matern52x2", "Matern52x3", "Matern52x4", "Matern32x4", "Matern32x3")     # test_gpu_parity.STACKED
 QUANTITIES = ("yhat", "x", "dx", "nll", "grad")
 FAMILIES = ("d2", "d3", "stacked")
 # row 2 of the two `unstable` draws and the third word of their seeds (see the docstring): test_gpu_parity's rho(AKHA) = 1.47 under the literal
@@ -123,26 +121,6 @@ FP32_BAR = {f: {q: min(REF32[f][q] * HALF_DECADE, TODAY32[q]) for q in QUANTITIE
 
 
 # ------------------------------------------------------------------------------------------------ the cases
-def synth(L, T, rng, nan_frac=0.0):
-    """The suite's stream (test_gpu_parity.synth)."""
-    t = np.arange(T)[None, :]; l = np.arange(L)[:, None]
-    Ty = np.sin(0.05 * t * (1 + l % 7)) + 0.1 * rng.standard_normal((L, T))
-    if nan_frac:
-        Ty[rng.random((L, T)) < nan_frac] = np.nan
-    return Ty
-
-
-def synth_params(L, rng):
-    return np.column_stack([rng.uniform(0.5, 2, L), rng.uniform(0.5, 2, L), rng.uniform(0.05, 0.2, L)])
-
-
-def synth_params_stacked(L, J, rng):
-    cols = []
-    for _ in range(J):
-        cols += [rng.uniform(0.5, 2, L), rng.uniform(0.5, 2, L)]
-    return np.column_stack(cols + [rng.uniform(0.05, 0.2, L)])
-
-
 def _k52(kern):
     return 1 if kern == "Matern52" else 0
 
@@ -181,10 +159,6 @@ def _cid(c):
 
 def family(kern):
     return "d2" if kern == "Matern32" else "d3" if kern == "Matern52" else "stacked"
-
-
-def _round32(a):
-    return np.asarray(a, dtype=np.float64).astype(np.float32).astype(np.float64)
 
 
 def _inputs(c):
@@ -230,7 +204,7 @@ def _inputs(c):
     P = prm.shape[1]
     d = (2 if kern.startswith("Matern32") else 3) * max(J, 1)
     x0 = 0.2 * rng.standard_normal((L, d)); dx0 = 0.05 * rng.standard_normal((L, P, d))
-    return prm, _round32(Ty), _round32(x0), _round32(dx0)         # fp32 numbers: one reference serves both precisions, input rounding is no error
+    return prm, round32(Ty), round32(x0), round32(dx0)         # fp32 numbers: one reference serves both precisions, input rounding is no error
 
 
 # ------------------------------------------------------------------------------------------------ the reference and its scales

@@ -9,75 +9,22 @@ import numpy as np
 import pytest
 import scipy.linalg as sl
 
-from conftest import ROOT, rel_err, rel_err_rows
-from oracle.moihgp_numpy import IHGP
-from test_forecast import padding_untouched, sentinel_out
-from test_smoother import KMAP, POOL, bank_and_tables, smooth_np, synth, tables, to_dev
+from conftest import rel_err, rel_err_rows
+from parity_support import synth
+from stream_reference import F_of, interp_np, interp_rows_np, project_np, smooth_np, tables
+from stream_support import (DT, FRACS1, FRACS3, FRACS8, KMAP, POOL, VAR_EDGE, VAR_INNER, assert_declared, assert_exported, bank_and_tables,
+                            cxx_fmt, cxx_rows, cxx_run, cxx_test_binary, end_to_end_inputs, env, gaps_edges_inplace, padding_untouched, pool_models,
+                            sentinel_out, to_dev, tol_of)  # noqa: F401  (env: the module's fixture)
+from stream_support import FP64_TIGHT as FP64_TOL
 
 INTERP_SYMBOLS = ("moihgp_interp_stream", "moihgp_interp_variances")
-FRACS1 = [0.5]                                              # one plane per replay
-FRACS3 = [0.25, 0.5, 0.75]                                  # two per replay, and a repeated replay whose second plane is idle
-FRACS8 = [0.0, 0.125, 0.9, 0.5, 0.25, 0.999, 0.75, 1e-3]    # four full replays, offset 0 among them
-FP64_TOL, FP32_TOL = 1e-9, 1e-3
-DT = 0.1
-# The variance (P_phi + G_phi (Ps - P) G_phi^T)_00 is a difference of terms of the size of P_00 and goes through P^-1, so an fp64 evaluation carries
-# a relative rounding error of the order of eps cond(P) P_00 / var.  On POOL's draw (1.3, 0.8, 1e-6) that is 3e-8 (eps = 2.2e-16, cond(P) = 1.5e4, P_00 = 9e-3,
-# var = 1e-6 near a tick), 1e-11 and less on the others.  Held against an 80-bit evaluation of the same formula, the numpy reference is good to 3e-12
-# over the whole POOL at the offsets VAR_INNER, but only to 5e-10 at VAR_EDGE (beside a tick, where var falls to var_smoothed): the library's
-# variances are compared at 1e-10 where the reference supports that, and at the rounding bound of the formula elsewhere.
-VAR_INNER = [0.125, 0.25, 0.5, 0.75]
-VAR_EDGE = [0.0, 1e-3, 0.9, 0.999]
 
 
 def var_edge_bound(tb, var):
     return max(1e-10, float(np.finfo(np.float64).eps * np.linalg.cond(tb["P"]) * tb["P"][0, 0] / var))
 
 
-def tol_of(dtype):
-    return FP64_TOL if dtype == "f64" else FP32_TOL
-
-
-# ------------------------------------------------------------------------------------------------ numpy definition
-def F_of(kern, dt, prm):
-    g = IHGP(dt, kern)
-    g.update(np.asarray(prm, dtype=np.float64))
-    return np.array(g.ss.F, dtype=np.float64)
-
-
-def interp_rows_np(tb, F, dt, phi):
-    """(a_phi, g_phi, var) of one latent and one offset, from the definition."""
-    Ap, Bp = sl.expm(F * (phi * dt)), sl.expm(F * ((1.0 - phi) * dt))
-    Pp = Ap @ tb["PF"] @ Ap.T + tb["Pinf"] - Ap @ tb["Pinf"] @ Ap.T
-    Gp = Pp @ Bp.T @ np.linalg.inv(tb["P"])
-    return Ap[0], Gp[0], (Pp + Gp @ (tb["Ps"] - tb["P"]) @ Gp.T)[0, 0]
-
-
-def interp_np(tbs, F_list, dt, fracs, Ty, x_in=None):
-    """fine[k][l][t] = a_k . xf[t] + g_k . s[t+1] with the smoother's two passes, vectorised over latents.
-    Returns (fine [K][L][T], ys [L][T], the end state [L][d], var [K][L])."""
-    A = np.stack([t["A"] for t in tbs]); K = np.stack([t["K"] for t in tbs]); G = np.stack([t["G"] for t in tbs])
-    L, T = Ty.shape
-    d = A.shape[1]
-    rows = [[interp_rows_np(tb, F, dt, phi) for tb, F in zip(tbs, F_list)] for phi in fracs]
-    a = np.array([[r[0] for r in rk] for rk in rows]); g = np.array([[r[1] for r in rk] for rk in rows])     # [K][L][d]
-    var = np.array([[r[2] for r in rk] for rk in rows])
-    x = np.zeros((L, d)) if x_in is None else np.array(x_in, dtype=np.float64)
-    p = np.zeros((L, T)); v = np.zeros((L, T)); xf = np.zeros((L, T, d))
-    for t in range(T):
-        xp = np.einsum("lij,lj->li", A, x)
-        p[:, t] = xp[:, 0]
-        y = Ty[:, t]
-        v[:, t] = np.where(np.isnan(y), 0.0, y - p[:, t])
-        x = xp + K * v[:, t:t + 1]
-        xf[:, t] = x
-    s = np.zeros((L, d)); ys = np.zeros((L, T)); fine = np.zeros((len(fracs), L, T))
-    for t in range(T - 1, -1, -1):
-        fine[:, :, t] = np.einsum("kld,ld->kl", a, xf[:, t]) + np.einsum("kld,ld->kl", g, s)
-        s = np.einsum("lij,lj->li", G, s) + K * v[:, t:t + 1]
-        ys[:, t] = p[:, t] + s[:, 0]
-    return fine, ys, x, var
-
-
+# ------------------------------------------------------------------------------------------------ cross-check of the numpy definition
 def dense_refined(tb, F, dt, y, n, ticks):
     """Mean and variance of the latent function on the grid dt / n at the points (t + j / n) dt, t in ticks, 0 <= j < n, given y observed at every
     n-th point, under the stationary GP prior with covariance (expm(F tau) Pinf)_00.  Returns (mean [n][len(ticks)], var [n][len(ticks)])."""
@@ -102,18 +49,12 @@ def dense_refined(tb, F, dt, y, n, ticks):
 
 # ------------------------------------------------------------------------------------------------ CPU
 def test_header_and_loader_declare_the_interp_entries():
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "moihgp.h")).read(), flags=re.S)
-    from multioutputihgp_amd import _lib
-    for n in INTERP_SYMBOLS:
-        assert re.search(r"\b%s\s*\(" % n, src), n
-        assert n in _lib.ADDITIVE_SYMBOLS, n
+    src = assert_declared(INTERP_SYMBOLS)
     assert re.search(r"#define\s+MOIHGP_INTERP_MAX_POINTS\s+8\b", src)
 
 
 def test_library_exports_the_interp_entries(hip_built):
-    lib = C.CDLL(hip_built)
-    for n in INTERP_SYMBOLS:
-        assert hasattr(lib, n), n
+    assert_exported(hip_built, INTERP_SYMBOLS)
 
 
 @pytest.mark.parametrize("kern", ["Matern32", "Matern52"])
@@ -210,57 +151,11 @@ def test_python_argument_validation():
             streams._frac_list(bad)
 
 
-def _cxx_interp(hip_built):
-    import subprocess
-    build = os.path.join(ROOT, "build", "cxx_tests")
-    os.makedirs(build, exist_ok=True)
-    exe = os.path.join(build, "interp_test")
-    libdir = os.path.dirname(hip_built)
-    subprocess.run(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cxx", "interp_test.cpp"),
-                    "-o", exe, "-L", libdir, "-lmoihgp", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    return exe
-
-
 def test_cxx_predict_between_compiles_and_links(hip_built):
-    assert os.path.exists(_cxx_interp(hip_built))
+    assert os.path.exists(cxx_test_binary(hip_built, "interp_test"))
 
 
 # ------------------------------------------------------------------------------------------------ GPU
-@pytest.fixture(scope="module")
-def env(hip_built):
-    import torch
-    assert torch.cuda.is_available(), "GPU suite needs a GPU"
-    torch.cuda.set_device(0)
-    from multioutputihgp_amd import streams
-    return dict(torch=torch, streams=streams)
-
-
-_MODEL = {}
-
-
-def model_of(kern, prm, dt=DT):
-    """(tables, F) of one parameter draw, computed once."""
-    key = (kern, tuple(prm), dt)
-    if key not in _MODEL:
-        _MODEL[key] = (tables(kern, dt, prm), F_of(kern, dt, prm))
-    return _MODEL[key]
-
-
-def pool_models(kern, L):
-    ms = [model_of(kern, POOL[l % len(POOL)]) for l in range(L)]
-    return [m[0] for m in ms], [m[1] for m in ms]
-
-
-def with_gaps(Ty, rng):
-    """Missing ticks at the two ends, on both sides of a chunk edge and of a segment edge (where the stream has them), and 1 % scattered."""
-    L, T = Ty.shape
-    for t in (0, T - 1, 15, 16, 1023, 1024):
-        if t < T:
-            Ty[:, t] = np.nan
-    Ty[rng.random((L, T)) < 0.01] = np.nan
-    return Ty
-
-
 _CASES = {}
 
 
@@ -272,7 +167,7 @@ def parity_case(kern, L, T):
         tbs, Fs = pool_models(kern, L)
         Ty = synth(L, T, rng)
         if T >= 16:
-            Ty = with_gaps(Ty, rng)
+            Ty = gaps_edges_inplace(Ty, rng)
         Ty = Ty.astype(np.float32).astype(np.float64)
         x0 = (0.1 * rng.standard_normal((L, Fs[0].shape[0]))).astype(np.float32).astype(np.float64)
         sets = [("1", FRACS1), ("3", FRACS3)] + ([("8", FRACS8)] if L == 7 else [])
@@ -536,28 +431,9 @@ def test_calls_on_two_streams_keep_their_own_tables(env):
         assert rel_err_rows(b[0][k].cpu().numpy(), case["ref"]["3"][k]) <= FP64_TOL
 
 
-def _end_to_end_inputs(rng, M, L, T, missing):
-    params = np.concatenate([(np.eye(M, L) + 0.2 * rng.standard_normal((M, L))).ravel(), rng.uniform(0.5, 2, L), [0.05],
-                             np.column_stack([rng.uniform(0.5, 2, L), rng.uniform(0.5, 2, L), rng.uniform(0.05, 0.2, L)]).ravel()])
-    Y = np.sin(0.02 * np.arange(T)[:, None] * (1 + np.arange(M)[None, :] % 5)) + 0.1 * rng.standard_normal((T, M))
-    if missing:
-        Y[rng.random((T, M)) < 0.02] = np.nan
-    return params, Y
-
-
 def _interp_outputs_np(gp, Y, kern, fracs):
-    M, L = gp.num_output, gp.num_latent
-    prm = gp.params
-    U, S = prm[:M * L].reshape(M, L), prm[M * L:M * L + L]
-    igp = prm[-3 * L:].reshape(L, 3)
-    Ty = np.zeros((L, Y.shape[0]))
-    for t, y in enumerate(Y):
-        obs = ~np.isnan(y)
-        if obs.sum() < L:
-            Ty[:, t] = np.nan
-            continue
-        U0 = U[obs]
-        Ty[:, t] = np.linalg.solve(U0.T @ U0, U0.T @ y[obs]) / np.sqrt(S)
+    U, S, igp, Ty = project_np(gp, Y, nan_below_L=True)
+    L = len(igp)
     tbs = [tables(kern, DT, igp[l]) for l in range(L)]
     fine, ys, _, var = interp_np(tbs, [F_of(kern, DT, igp[l]) for l in range(L)], DT, fracs, Ty)
     mix = U * np.sqrt(S)
@@ -574,7 +450,7 @@ def test_interpolate_and_upsample_outputs_end_to_end(env, kern, missing):
     rng = np.random.default_rng(27)
     M, L, T, factor = 12, 4, 600, 4
     fracs = [j / factor for j in range(1, factor)]
-    params, Y = _end_to_end_inputs(rng, M, L, T, missing)
+    params, Y = end_to_end_inputs(rng, M, L, T, missing)
     gp = MOIHGP(DT, M, L, kernel=KMAP[kern])
     gp.update(params)
     Yd = torch.from_numpy(Y).cuda()
@@ -617,19 +493,17 @@ def test_interpolate_outputs_raises_on_a_failed_latent(env):
 @pytest.mark.gpu
 @pytest.mark.parametrize("kern", ["Matern32", "Matern52"])
 def test_cxx_predict_between_matches_python(env, hip_built, kern):
-    import subprocess
     torch, streams = env["torch"], env["streams"]
     from multioutputihgp_amd import MOIHGP
     rng = np.random.default_rng(28)
     M, L, T, frac = 12, 4, 300, 0.375
-    params, Y = _end_to_end_inputs(rng, M, L, T, True)
-    fmt = lambda a: " ".join("nan" if np.isnan(v) else repr(float(v)) for v in np.ravel(a))
-    exe = _cxx_interp(hip_built)
+    params, Y = end_to_end_inputs(rng, M, L, T, True)
+    exe = cxx_test_binary(hip_built, "interp_test")
 
     def run(fr):
-        inp = f"{0 if kern == 'Matern32' else 1} {M} {L} 0.1 {fr!r} {T}\n{fmt(params)}\n" + "\n".join(fmt(y) for y in Y) + "\n"
-        return subprocess.run([exe], input=inp, capture_output=True, text=True, check=True).stdout.strip().split("\n")
-    got = np.array([[float(v) for v in line.split()] for line in run(frac)])
+        inp = f"{0 if kern == 'Matern32' else 1} {M} {L} 0.1 {fr!r} {T}\n{cxx_fmt(params)}\n" + "\n".join(cxx_fmt(y) for y in Y) + "\n"
+        return cxx_run(exe, inp)
+    got = cxx_rows(run(frac))
     gp = MOIHGP(DT, M, L, kernel=KMAP[kern])
     gp.update(params)
     Yfine, _, _, _ = streams.interpolate_outputs(gp, torch.from_numpy(Y).cuda(), [frac])

@@ -8,41 +8,20 @@ import numpy as np
 import pytest
 import scipy.linalg as sl
 
-from conftest import ROOT, rel_err, rel_err_rows
-from test_forecast import padding_untouched, sentinel_out
-from test_smoother import KMAP, POOL, bank_and_tables, smooth_np, synth, tables, to_dev
+from conftest import rel_err, rel_err_rows
+from parity_support import synth
+from stream_reference import forward_np, lagged_np, lagged_var_np, project_np, smooth_np, tables
+from stream_support import (FP32_TOL, KMAP, LAGS8, LMAX, POOL, assert_declared, assert_exported, bank_and_tables, cxx_fmt, cxx_rows, cxx_run,
+                            cxx_test_binary, end_to_end_inputs, env, gaps_edges_blocks_inplace, padding_untouched, sentinel_out, to_dev,
+                            tol_of)  # noqa: F401  (env: the module's fixture)
+from stream_support import FP64_TIGHT as FP64_TOL
 
 LAGGED_SYMBOLS = ("moihgp_lagged_stream", "moihgp_lagged_variances")
-LMAX = 1 << 20
-LAGS8 = [0, 1, 15, 16, 17, 1023, 1024, LMAX]      # the chunk and segment edges of the shifted read, and a lag past the end
 LAGS1 = [5]                                       # one lag per replay
 LAGS3 = [40, 0, 2]                                # two per replay, and a repeated replay whose second plane is idle
-FP64_TOL, FP32_TOL = 1e-9, 1e-3
 
 
-def tol_of(dtype):
-    return FP64_TOL if dtype == "f64" else FP32_TOL
-
-
-# ------------------------------------------------------------------------------------------------ numpy definition
-def forward_np(tbs, Ty, x_in=None, state_at=None):
-    """The smoother's forward pass, vectorised over latents: p, v [L][T] and the filtered state after tick state_at - 1 (default T; 0: x_in)."""
-    A = np.stack([t["A"] for t in tbs]); K = np.stack([t["K"] for t in tbs])
-    L, T = Ty.shape
-    x = np.zeros((L, A.shape[1])) if x_in is None else np.array(x_in, dtype=np.float64)
-    state_at = T if state_at is None else state_at
-    p = np.zeros((L, T)); v = np.zeros((L, T)); xs = x.copy()
-    for t in range(T):
-        xp = np.einsum("lij,lj->li", A, x)
-        p[:, t] = xp[:, 0]
-        y = Ty[:, t]
-        v[:, t] = np.where(np.isnan(y), 0.0, y - p[:, t])
-        x = xp + K * v[:, t:t + 1]
-        if t + 1 == state_at:
-            xs = x.copy()
-    return p, v, xs
-
-
+# ------------------------------------------------------------------------------------------------ cross-checks of the numpy definition
 def lagged_direct_np(tb, y, lags, x_in=None):
     """The definition, one latent: lag[k][t] = p[t] + (sum_{j=0..l_k, t+j<T} G^j K v[t+j])_0, as a direct sum."""
     p, v, _ = forward_np([tb], y[None, :], None if x_in is None else x_in[None, :])
@@ -56,38 +35,6 @@ def lagged_direct_np(tb, y, lags, x_in=None):
         J = min(int(l) + 1, T)
         out[k] = p + np.correlate(np.concatenate([v, np.zeros(J - 1)]), u[:J], "valid")
     return out
-
-
-_WCACHE = {}
-
-
-def _window_gain(tb, l):
-    key = (tb["G"].tobytes(), tb["K"].tobytes(), int(l))
-    if key not in _WCACHE:
-        _WCACHE[key] = np.linalg.matrix_power(tb["G"], int(l) + 1) @ tb["K"]
-    return _WCACHE[key]
-
-
-def lagged_np(tbs, Ty, lags, x_in=None, state_at=None):
-    """The same by the backward recursion s_k[t] = G s_k[t+1] + K v[t] - G^(l_k+1) K v[t+l_k+1], vectorised over lags and latents.
-    Returns (lag [K][L][T], p [L][T], the filtered state after tick state_at - 1)."""
-    p, v, xs = forward_np(tbs, Ty, x_in, state_at)
-    L, T = Ty.shape
-    G = np.stack([t["G"] for t in tbs]); K = np.stack([t["K"] for t in tbs])
-    W = np.array([[_window_gain(t, l) for t in tbs] for l in lags])                    # [K][L][d]
-    nk = len(lags)
-    s = np.zeros((nk, L, G.shape[1])); out = np.zeros((nk, L, T)); vs = np.zeros((nk, L))
-    for t in range(T - 1, -1, -1):
-        for k, l in enumerate(lags):
-            vs[k] = v[:, t + l + 1] if t + l + 1 < T else 0.0
-        s = np.einsum("lij,klj->kli", G, s) + K[None] * v[None, :, t, None] - W * vs[:, :, None]
-        out[:, :, t] = p[None, :, t] + s[:, :, 0]
-    return out, p, xs
-
-
-def lagged_var_np(tb, l):
-    Gl = np.linalg.matrix_power(tb["G"], int(l))
-    return (tb["Ps"] + Gl @ (tb["PF"] - tb["Ps"]) @ Gl.T)[0, 0]
 
 
 def dense_lagged(tb, y, ticks, lags):
@@ -116,18 +63,12 @@ def dense_lagged(tb, y, ticks, lags):
 
 # ------------------------------------------------------------------------------------------------ CPU
 def test_header_and_loader_declare_the_lagged_entries():
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "moihgp.h")).read(), flags=re.S)
-    from multioutputihgp_amd import _lib
-    for n in LAGGED_SYMBOLS:
-        assert re.search(r"\b%s\s*\(" % n, src), n
-        assert n in _lib.ADDITIVE_SYMBOLS, n
+    src = assert_declared(LAGGED_SYMBOLS)
     assert re.search(r"#define\s+MOIHGP_LAGGED_MAX_LAGS\s+8\b", src)
 
 
 def test_library_exports_the_lagged_entries(hip_built):
-    lib = C.CDLL(hip_built)
-    for n in LAGGED_SYMBOLS:
-        assert hasattr(lib, n), n
+    assert_exported(hip_built, LAGGED_SYMBOLS)
 
 
 def _series(T, rng, gaps):
@@ -194,35 +135,10 @@ def test_python_argument_validation():
 
 
 def test_cxx_predict_lagged_compiles_and_links(hip_built):
-    assert os.path.exists(_cxx_lagged(hip_built))
+    assert os.path.exists(cxx_test_binary(hip_built, "lagged_test"))
 
 
 # ------------------------------------------------------------------------------------------------ GPU
-@pytest.fixture(scope="module")
-def env(hip_built):
-    import torch
-    assert torch.cuda.is_available(), "GPU suite needs a GPU"
-    torch.cuda.set_device(0)
-    from multioutputihgp_amd import streams
-    return dict(torch=torch, streams=streams)
-
-
-def with_gaps(Ty, rng):
-    """Missing ticks at the two ends, on both sides of a chunk edge and of a segment edge, one whole chunk, one whole segment, and 1 % scattered
-    (whatever of these the stream is long enough for)."""
-    L, T = Ty.shape
-    Ty[:, 0] = np.nan; Ty[:, T - 1] = np.nan
-    for t in (15, 16, 1023, 1024):
-        if t < T:
-            Ty[:, t] = np.nan
-    if T >= 63:
-        Ty[::2, 32:48] = np.nan
-        Ty[rng.random((L, T)) < 0.01] = np.nan
-    if T >= 2048:
-        Ty[1::2, 1024:2048] = np.nan
-    return Ty
-
-
 _CASES = {}
 
 
@@ -235,7 +151,7 @@ def parity_case(kern, L, T, gaps):
         tbs = [tbs[l % len(POOL)] for l in range(L)]
         Ty = synth(L, T, rng)
         if gaps:
-            Ty = with_gaps(Ty, rng)
+            Ty = gaps_edges_blocks_inplace(Ty, rng)
         Ty = Ty.astype(np.float32).astype(np.float64)
         x0 = (0.1 * rng.standard_normal((L, tbs[0]["A"].shape[0]))).astype(np.float32).astype(np.float64)
         ref, p, xe = lagged_np(tbs, Ty, LAGS8 + LAGS1 + LAGS3, x0)
@@ -316,7 +232,7 @@ def test_family_identities_on_the_device(env, kern, dtype):
     rng = np.random.default_rng(21)
     L, T = 7, 2100
     bank, _, _ = bank_and_tables(streams, kern, L)
-    Ty = with_gaps(synth(L, T, rng), rng)
+    Ty = gaps_edges_blocks_inplace(synth(L, T, rng), rng)
     dev = to_dev(torch, Ty, tdt, T)
     lg, ypred, xl, _ = bank.lagged(dev, [0, T, LMAX])
     fc, xf, _ = bank.forecast(dev, [0, 1], gains="kalman")
@@ -607,31 +523,11 @@ def test_calls_on_two_streams_keep_their_own_tables(env):
 
 
 def _lagged_outputs_np(gp, Y, kern, lags):
-    M, L = gp.num_output, gp.num_latent
-    prm = gp.params
-    U, S = prm[:M * L].reshape(M, L), prm[M * L:M * L + L]
-    igp = prm[-3 * L:].reshape(L, 3)
-    Ty = np.zeros((L, Y.shape[0]))
-    for t, y in enumerate(Y):
-        obs = ~np.isnan(y)
-        if obs.sum() < L:
-            Ty[:, t] = np.nan
-            continue
-        U0 = U[obs]
-        Ty[:, t] = np.linalg.solve(U0.T @ U0, U0.T @ y[obs]) / np.sqrt(S)
-    tbs = [tables(kern, 0.1, igp[l]) for l in range(L)]
+    U, S, igp, Ty = project_np(gp, Y, nan_below_L=True)
+    tbs = [tables(kern, 0.1, igp[l]) for l in range(len(igp))]
     lg, _, _ = lagged_np(tbs, Ty, lags)
     var = np.array([[lagged_var_np(tb, l) for tb in tbs] for l in lags])
     return np.einsum("ml,klt->ktm", U * np.sqrt(S), lg), (S[None, :] * var) @ (U ** 2).T
-
-
-def _end_to_end_inputs(rng, M, L, T, missing):
-    params = np.concatenate([(np.eye(M, L) + 0.2 * rng.standard_normal((M, L))).ravel(), rng.uniform(0.5, 2, L), [0.05],
-                             np.column_stack([rng.uniform(0.5, 2, L), rng.uniform(0.5, 2, L), rng.uniform(0.05, 0.2, L)]).ravel()])
-    Y = np.sin(0.02 * np.arange(T)[:, None] * (1 + np.arange(M)[None, :] % 5)) + 0.1 * rng.standard_normal((T, M))
-    if missing:
-        Y[rng.random((T, M)) < 0.02] = np.nan
-    return params, Y
 
 
 @pytest.mark.gpu
@@ -642,7 +538,7 @@ def test_lagged_outputs_end_to_end(env, kern, missing):
     from multioutputihgp_amd import MOIHGP
     rng = np.random.default_rng(27)
     M, L, T, lags = 6, 3, 300, [0, 4, 25, 300]
-    params, Y = _end_to_end_inputs(rng, M, L, T, missing)
+    params, Y = end_to_end_inputs(rng, M, L, T, missing)
     gp = MOIHGP(0.1, M, L, kernel=KMAP[kern])
     gp.update(params)
     Yl, var = streams.lagged_outputs(gp, torch.from_numpy(Y).cuda(), lags)
@@ -657,30 +553,17 @@ def test_lagged_outputs_end_to_end(env, kern, missing):
 
 
 # ------------------------------------------------------------------------------------------------ C++ (predictLagged)
-def _cxx_lagged(hip_built):
-    import subprocess
-    build = os.path.join(ROOT, "build", "cxx_tests")
-    os.makedirs(build, exist_ok=True)
-    exe = os.path.join(build, "lagged_test")
-    libdir = os.path.dirname(hip_built)
-    subprocess.run(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cxx", "lagged_test.cpp"),
-                    "-o", exe, "-L", libdir, "-lmoihgp", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    return exe
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("kern", ["Matern32", "Matern52"])
 def test_cxx_predict_lagged_matches_python(env, hip_built, kern):
-    import subprocess
     torch, streams = env["torch"], env["streams"]
     from multioutputihgp_amd import MOIHGP
     rng = np.random.default_rng(28)
     M, L, T, lag = 12, 4, 300, 6
-    params, Y = _end_to_end_inputs(rng, M, L, T, True)
-    fmt = lambda a: " ".join("nan" if np.isnan(v) else repr(float(v)) for v in np.ravel(a))
-    inp = f"{0 if kern == 'Matern32' else 1} {M} {L} 0.1 {lag} {T}\n{fmt(params)}\n" + "\n".join(fmt(y) for y in Y) + "\n"
-    out = subprocess.run([_cxx_lagged(hip_built)], input=inp, capture_output=True, text=True, check=True).stdout.strip().split("\n")
-    got = np.array([[float(v) for v in line.split()] for line in out])
+    params, Y = end_to_end_inputs(rng, M, L, T, True)
+    inp = f"{0 if kern == 'Matern32' else 1} {M} {L} 0.1 {lag} {T}\n{cxx_fmt(params)}\n" + "\n".join(cxx_fmt(y) for y in Y) + "\n"
+    out = cxx_run(cxx_test_binary(hip_built, "lagged_test"), inp)
+    got = cxx_rows(out)
     gp = MOIHGP(0.1, M, L, kernel=KMAP[kern])
     gp.update(params)
     Yl, _ = streams.lagged_outputs(gp, torch.from_numpy(Y).cuda(), [lag])

@@ -58,12 +58,10 @@ import numpy as np
 import pytest
 
 from conftest import rel_err, rel_err_rows
+from parity_support import FP32_TOL, FP64_TIGHT, KMAP, synth
 
-FP64_TIGHT = 1e-9
-FP32_TOL = 1e-3
 ORACLES_AGREE = 1e-11
 CALM = 1e3
-KMAP = {"Matern32": "Matern32", "Matern52": "Matern52ss"}
 REF_KERNELS = ("Matern32", "Matern52")
 REF_DTS = (1e-3, 1e-2, 0.1, 1.0)
 STACKED_KERNELS = ("Matern32x2", "Matern52x2", "Matern52x4")
@@ -89,15 +87,6 @@ PADE_CLASSES = ("degree 3", "degree 5", "degree 7", "degree 9", "degree 13, no s
 
 def _cid(cell):
     return "%s-%s-dt%g" % cell
-
-
-def synth(L, T, rng, nan_frac=0.0):
-    """The suite's stream (test_gpu_parity.synth)."""
-    t = np.arange(T)[None, :]; l = np.arange(L)[:, None]
-    Ty = np.sin(0.05 * t * (1 + l % 7)) + 0.1 * rng.standard_normal((L, T))
-    if nan_frac:
-        Ty[rng.random((L, T)) < nan_frac] = np.nan
-    return Ty
 
 
 # ------------------------------------------------------------------------------------------------ the draw and its inclusion masks (CPU)

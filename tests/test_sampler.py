@@ -3,143 +3,22 @@ generator against Random123's known answers, the innovations realization of the 
 covariance (CPU) -- then the library's generator, tables and sweeps against it (GPU)."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
 
-from conftest import ROOT, rel_err
-from test_smoother import KMAP, POOL, bank_and_tables, env, synth, tables, to_dev, _smooth_outputs_np  # noqa: F401  (env: the module's fixture)
+from conftest import rel_err
+from parity_support import synth
+from stream_reference import acov_hat, deviations_np, noise_np, philox4x32_10, realization, smooth_outputs_np, tables
+from stream_support import (KMAP, POOL, assert_declared, assert_exported, bank_and_tables, cxx_fmt, cxx_rows, cxx_run, cxx_test_binary,
+                            end_to_end_inputs, env, to_dev)  # noqa: F401  (env: the module's fixture)
 
 SAMPLE_SYMBOLS = ("moihgp_sample_stream", "moihgp_sample_noise", "moihgp_get_sampler")
 GROUP = 8          # samples per wavefront of sample_sweep_kernel (sampler.hip kSampleGroup)
 SEED = (0x9E3779B9 << 32) | 0x1234567          # a non-zero high word
 
 
-# ------------------------------------------------------------------------------------------------ numpy definition: the generator
-def philox4x32_10(ctr, key):
-    """Random123's Philox4x32-10: ctr [..., 4], key [..., 2] (uint32) -> [..., 4]."""
-    c = [np.asarray(ctr[..., i], dtype=np.uint64) for i in range(4)]
-    k = [np.asarray(key[..., i], dtype=np.uint64) for i in range(2)]
-    m32 = np.uint64(0xFFFFFFFF)
-    for _ in range(10):
-        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
-        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k[0], p1 & m32, (p0 >> np.uint64(32)) ^ c[3] ^ k[1], p0 & m32]
-        k = [(k[0] + np.uint64(0x9E3779B9)) & m32, (k[1] + np.uint64(0xBB67AE85)) & m32]
-    return np.stack(c, axis=-1).astype(np.uint32)
-
-
-def _pair_normals(a, b):
-    """The header's word pair -> two normals: u1, u2 and the angle in fp32 as on the device, the functions in fp64 (the reference)."""
-    f = np.float32
-    u1 = ((a >> np.uint32(8)).astype(f) + f(0.5)) * f(2.0 ** -24)
-    u2 = ((b >> np.uint32(8)).astype(f) + f(0.5)) * f(2.0 ** -24)
-    rho = np.sqrt(-2.0 * np.log(u1.astype(np.float64)))
-    ang = (f(6.283185307179586) * u2).astype(np.float64)
-    return rho * np.cos(ang), rho * np.sin(ang)
-
-
-def normals4(seed, q, latent, sample, tag):
-    """[..., 4] normals of the counters (q, latent, sample, tag) (broadcast), key = the seed's two words."""
-    q, latent, sample, tag = np.broadcast_arrays(*[np.asarray(v, dtype=np.uint64) for v in (q, latent, sample, tag)])
-    ctr = np.stack([q, latent, sample, tag], axis=-1) & np.uint64(0xFFFFFFFF)
-    key = np.broadcast_to(np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint64), ctr.shape[:-1] + (2,))
-    w = philox4x32_10(ctr, key)
-    n0, n1 = _pair_normals(w[..., 0], w[..., 1])
-    n2, n3 = _pair_normals(w[..., 2], w[..., 3])
-    return np.stack([n0, n1, n2, n3], axis=-1)
-
-
-def noise_np(seed, latent0, L, sample0, S, T):
-    """(noise [S, L, T], start [S, L, 4]) of moihgp_sample_noise."""
-    s = sample0 + np.arange(S)[:, None, None]
-    l = latent0 + np.arange(L)[None, :, None]
-    nq = (T + 3) // 4
-    noise = normals4(seed, np.arange(nq)[None, None, :], l, s, 0).reshape(S, L, 4 * nq)[:, :, :T]
-    return noise, normals4(seed, 0, l[:, :, 0], s[:, :, 0], 1)
-
-
-# ------------------------------------------------------------------------------------------------ numpy definition: the realization
-def realization(G, Ps, nfix=64, nnewton=8):
-    """Sigma with sigma^2 = r0 - Sigma_00, B = G (N - Sigma h) / sigma^2, Sigma = G Sigma G^T + sigma^2 B B^T: 64 steps of the iteration from zero,
-    then up to 8 Newton steps dSigma - Ac dSigma Ac^T = F(Sigma), Ac = G - B h^T; and the header's acceptance figure."""
-    d = G.shape[0]
-    N, r0 = Ps[:, 0].copy(), Ps[0, 0]
-    Sg = np.zeros((d, d))
-
-    def parts(Sg):
-        s2 = r0 - Sg[0, 0]
-        B = G @ (N - Sg[:, 0]) / s2
-        F = G @ Sg @ G.T + s2 * np.outer(B, B) - Sg
-        return s2, B, (F + F.T) / 2
-
-    with np.errstate(all="ignore"):
-        for _ in range(nfix):
-            Sg = Sg + parts(Sg)[2]
-        for _ in range(nnewton):
-            s2, B, F = parts(Sg)
-            m = np.max(np.abs(Sg))
-            if not np.isfinite(m) or not np.max(np.abs(F)) > 1e-15 * m:      # relative to max |Sigma|, not r0
-                break
-            Ac = G.copy(); Ac[:, 0] -= B
-            try:
-                dS = np.linalg.solve(np.eye(d * d) - np.kron(Ac, Ac), F.ravel()).reshape(d, d)
-            except np.linalg.LinAlgError:
-                break
-            if not np.all(np.isfinite(dS)):
-                break
-            Sg = Sg + (dS + dS.T) / 2
-        s2, B, _ = parts(Sg)
-        r, rh = acov(G, N, 64), acov_hat(G, Sg, s2, B, 64)
-        err = float(np.max(np.abs(rh - r)) / r0)
-    ok = np.isfinite(err) and err <= 1e-9 and s2 > 0 and np.all(np.isfinite(Sg)) and np.all(np.isfinite(B))
-    return dict(B=B, sigma2=float(s2), Sigma=Sg, Lc=chol_zero(Sg), err=err, status=0 if ok else 2)
-
-
-def acov(G, N, n):
-    """r[k] = H G^k Ps H^T, k < n."""
-    out, v = np.zeros(n), N.copy()
-    for k in range(n):
-        out[k] = v[0]; v = G @ v
-    return out
-
-
-def acov_hat(G, Sg, s2, B, n):
-    """r^[0] = Sigma_00 + sigma^2, r^[k] = (G^(k-1) (G Sigma h + sigma^2 B))_0."""
-    out, w = np.zeros(n), G @ Sg[:, 0] + s2 * B
-    out[0] = Sg[0, 0] + s2
-    for k in range(1, n):
-        out[k] = w[0]; w = G @ w
-    return out
-
-
-def chol_zero(S):
-    """Lower Cholesky factor of sym(S); a pivot <= 0 gives a zero column."""
-    d = S.shape[0]
-    S, Lc = (S + S.T) / 2, np.zeros((d, d))
-    for j in range(d):
-        p = S[j, j] - Lc[j, :j] @ Lc[j, :j]
-        if not p > 0:
-            continue
-        Lc[j, j] = np.sqrt(p)
-        for i in range(j + 1, d):
-            Lc[i, j] = (S[i, j] - Lc[i, :j] @ Lc[j, :j]) / Lc[j, j]
-    return Lc
-
-
-def deviations_np(G, B, sigma, Lc, noise, start):
-    """o [S, L, T] of the header's backward recursion: G [L, d, d], B [L, d], sigma [L], Lc [L, d, d], noise [S, L, T], start [S, L, 4]."""
-    S, L, T = noise.shape
-    d = G.shape[1]
-    u = np.einsum("lij,slj->sli", Lc, start[:, :, :d])
-    o = np.zeros((S, L, T))
-    for t in range(T - 1, -1, -1):
-        e = sigma[None, :] * noise[:, :, t]
-        o[:, :, t] = u[:, :, 0] + e
-        u = np.einsum("lij,slj->sli", G, u) + B[None] * e[:, :, None]
-    return o
-
-
+# ------------------------------------------------------------------------------------------------ cross-check of the numpy definition
 def dense_posterior_cov(tb, T):
     A, Pinf, R = tb["A"], tb["Pinf"], tb["R"]
     c = np.zeros(T); M = np.eye(A.shape[0])
@@ -152,17 +31,11 @@ def dense_posterior_cov(tb, T):
 
 # ------------------------------------------------------------------------------------------------ CPU
 def test_header_and_loader_declare_the_sampler():
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "moihgp.h")).read(), flags=re.S)
-    from multioutputihgp_amd import _lib
-    for n in SAMPLE_SYMBOLS:
-        assert re.search(r"\b%s\s*\(" % n, src), n
-        assert n in _lib.ADDITIVE_SYMBOLS, n
+    assert_declared(SAMPLE_SYMBOLS)
 
 
 def test_library_exports_the_sampler(hip_built):
-    lib = C.CDLL(hip_built)
-    for n in SAMPLE_SYMBOLS:
-        assert hasattr(lib, n), n
+    assert_exported(hip_built, SAMPLE_SYMBOLS)
 
 
 def test_numpy_philox_gives_the_known_answers():
@@ -208,7 +81,7 @@ def test_numpy_realization_over_the_learners_box():
 
 
 def test_cxx_sample_smoothed_compiles_and_links(hip_built):
-    assert os.path.exists(_cxx_sampler(hip_built))
+    assert os.path.exists(cxx_test_binary(hip_built, "sampler_test"))
 
 
 # ------------------------------------------------------------------------------------------------ GPU: the generator
@@ -513,15 +386,6 @@ def test_sample_outputs_raises_on_a_failed_latent(env):
 
 
 # ------------------------------------------------------------------------------------------------ GPU: end to end
-def _problem(rng, M, L, T, missing):
-    params = np.concatenate([(np.eye(M, L) + 0.2 * rng.standard_normal((M, L))).ravel(), rng.uniform(0.5, 2, L), [0.05],
-                             np.column_stack([rng.uniform(0.5, 2, L), rng.uniform(0.5, 2, L), rng.uniform(0.05, 0.2, L)]).ravel()])
-    Y = np.sin(0.02 * np.arange(T)[:, None] * (1 + np.arange(M)[None, :] % 5)) + 0.1 * rng.standard_normal((T, M))
-    if missing:
-        Y[rng.random((T, M)) < 0.02] = np.nan
-    return params, Y
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("kern", ["Matern32", "Matern52"])
 @pytest.mark.parametrize("missing", [False, True])
@@ -529,7 +393,7 @@ def test_sample_outputs_end_to_end(env, kern, missing):
     torch, streams = env["torch"], env["streams"]
     from multioutputihgp_amd import MOIHGP
     M, L, T, S = 6, 3, 300, 3
-    params, Y = _problem(np.random.default_rng(26), M, L, T, missing)
+    params, Y = end_to_end_inputs(np.random.default_rng(26), M, L, T, missing)
     gp = MOIHGP(0.1, M, L, kernel=KMAP[kern])
     gp.update(params)
     Yd = torch.from_numpy(Y).cuda()
@@ -537,7 +401,7 @@ def test_sample_outputs_end_to_end(env, kern, missing):
     Ysm, var_s = streams.smooth_outputs(gp, Yd)
     torch.cuda.synchronize()
     assert Ys.shape == (S, T, M) and torch.equal(Ymean, Ysm) and np.array_equal(var, var_s)
-    ref_mean, ref_var = _smooth_outputs_np(gp, Y, kern)
+    ref_mean, ref_var = smooth_outputs_np(gp, Y, kern)
     assert rel_err(Ymean.T.cpu().numpy(), ref_mean) <= 1e-9 and rel_err(var, ref_var) <= 1e-10
     prm = gp.params
     U, Sc = prm[:M * L].reshape(M, L), prm[M * L:M * L + L]
@@ -565,29 +429,16 @@ def test_sample_outputs_end_to_end(env, kern, missing):
     assert np.all(diff <= bound), (diff, bound)
 
 
-def _cxx_sampler(hip_built):
-    import subprocess
-    build = os.path.join(ROOT, "build", "cxx_tests")
-    os.makedirs(build, exist_ok=True)
-    exe = os.path.join(build, "sampler_test")
-    libdir = os.path.dirname(hip_built)
-    subprocess.run(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cxx", "sampler_test.cpp"),
-                    "-o", exe, "-L", libdir, "-lmoihgp", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    return exe
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("kern", ["Matern32", "Matern52"])
 def test_cxx_sample_smoothed_matches_python(env, hip_built, kern):
-    import subprocess
     torch, streams = env["torch"], env["streams"]
     from multioutputihgp_amd import MOIHGP
     M, L, T, S = 12, 4, 300, 2
-    params, Y = _problem(np.random.default_rng(27), M, L, T, True)
-    fmt = lambda a: " ".join("nan" if np.isnan(v) else repr(float(v)) for v in np.ravel(a))
-    inp = f"{0 if kern == 'Matern32' else 1} {M} {L} 0.1 {T} {S} {SEED}\n{fmt(params)}\n" + "\n".join(fmt(y) for y in Y) + "\n"
-    out = subprocess.run([_cxx_sampler(hip_built)], input=inp, capture_output=True, text=True, check=True).stdout.strip().split("\n")
-    got = np.array([[float(v) for v in line.split()] for line in out]).reshape(S, T, M)
+    params, Y = end_to_end_inputs(np.random.default_rng(27), M, L, T, True)
+    inp = f"{0 if kern == 'Matern32' else 1} {M} {L} 0.1 {T} {S} {SEED}\n{cxx_fmt(params)}\n" + "\n".join(cxx_fmt(y) for y in Y) + "\n"
+    out = cxx_run(cxx_test_binary(hip_built, "sampler_test"), inp)
+    got = cxx_rows(out).reshape(S, T, M)
     gp = MOIHGP(0.1, M, L, kernel=KMAP[kern])
     gp.update(params)
     Ys, _, _ = streams.sample_outputs(gp, torch.from_numpy(Y).cuda(), S, seed=SEED)

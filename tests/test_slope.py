@@ -1,6 +1,6 @@
 """Slopes of whole streams (include/moihgp.h moihgp_slope_stream / _variances): the numpy definition the GPU is held to -- the time derivative of
 the off-grid smoother's mean and that derivative's own variance, pinned against the dense GP posterior of f' on a refined grid, against the rows one
-would write first (component 1 of the smoothed state, wrong for the reference's Matern-5/2) and against differences of test_interp's interp_np (CPU)
+would write first (component 1 of the smoothed state, wrong for the reference's Matern-5/2) and against differences of the off-grid smoother's interp_np (CPU)
 -- then the library's tables and sweeps against it (GPU).
 
 fp32 streams: the bounds come from sweeps_np(..., emulate32=True), which rounds p, v, the planes between the two passes and the results to fp32
@@ -18,10 +18,12 @@ import numpy as np
 import pytest
 import scipy.linalg as sl
 
-from conftest import ROOT, rel_err, rel_err_rows
-from test_forecast import padding_untouched, sentinel_out
-from test_interp import DT, FRACS1, FRACS3, FRACS8, VAR_EDGE, VAR_INNER, F_of, _end_to_end_inputs, interp_np, pool_models, with_gaps
-from test_smoother import KMAP, POOL, bank_and_tables, synth, tables, to_dev
+from conftest import rel_err, rel_err_rows
+from parity_support import synth
+from stream_reference import F_of, interp_np, project_np, slope_np, slope_rows_np, sweeps_np, tables
+from stream_support import (DT, FRACS1, FRACS3, FRACS8, KMAP, POOL, VAR_EDGE, VAR_INNER, assert_declared, assert_exported, bank_and_tables, cxx_fmt,
+                            cxx_rows, cxx_run, cxx_test_binary, end_to_end_inputs, env, gaps_edges_inplace, padding_untouched, pool_models,
+                            sentinel_out, to_dev)  # noqa: F401  (env: the module's fixture)
 
 SLOPE_SYMBOLS = ("moihgp_slope_stream", "moihgp_slope_variances")
 GIVEN = ("all", "past")
@@ -33,62 +35,17 @@ PARITY_L = [1, 7, 256]
 PARITY_T = [1, 2, 16, 17, 1024, 1025, 2065]
 
 
-def tol_of(dtype, ysmooth=False):
+def slope_tol_of(dtype, ysmooth=False):
     return FP64_TOL if dtype == "f64" else (FP32_TOL_YS if ysmooth else FP32_TOL)
 
 
-# ------------------------------------------------------------------------------------------------ numpy definition
-def slope_rows_np(tb, F, dt, phi, given="all"):
-    """(a, gd, var) of one latent and one offset, from the definition."""
-    Ap, Bp = sl.expm(F * (phi * dt)), sl.expm(F * ((1.0 - phi) * dt))
-    Pinf, P = tb["Pinf"], tb["P"]
-    Pp = Ap @ tb["PF"] @ Ap.T + Pinf - Ap @ Pinf @ Ap.T
-    if given == "past":
-        return Ap[1], np.zeros(F.shape[0]), Pp[1, 1]
-    gd = ((F @ (Pp - Pinf) - Pinf @ F.T) @ Bp.T @ np.linalg.inv(P))[0]
-    return Ap[1], gd, Pp[1, 1] + gd @ (tb["Ps"] - P) @ gd
-
-
+# ------------------------------------------------------------------------------------------------ cross-checks of the numpy definition
 def naive_rows_np(tb, F, dt, phi):
     """The rows one writes first: component 1 of the smoothed state at the inserted point, e1^T A_phi and e1^T G_phi, with the matching "variance"."""
     Ap, Bp = sl.expm(F * (phi * dt)), sl.expm(F * ((1.0 - phi) * dt))
     Pp = Ap @ tb["PF"] @ Ap.T + tb["Pinf"] - Ap @ tb["Pinf"] @ Ap.T
     Gp = Pp @ Bp.T @ np.linalg.inv(tb["P"])
     return Ap[1], Gp[1], (Pp + Gp @ (tb["Ps"] - tb["P"]) @ Gp.T)[1, 1]
-
-
-def sweeps_np(tbs, a, g, Ty, x_in=None, emulate32=False):
-    """plane[k][l][t] = a[k][l] . xf[t] + g[k][l] . s[t+1] with the smoother's two passes, vectorised over latents; returns (planes, ys, end state).
-    emulate32: p, v, the planes between the two passes and the results are rounded to fp32 where the kernels stage an fp32 stream (the forward
-    pass itself keeps v in fp64; the data are taken to be fp32 numbers already)."""
-    r32 = (lambda z: np.asarray(z, dtype=np.float32).astype(np.float64)) if emulate32 else (lambda z: z)
-    A = np.stack([t["A"] for t in tbs]); K = np.stack([t["K"] for t in tbs]); G = np.stack([t["G"] for t in tbs])
-    L, T = Ty.shape
-    d = A.shape[1]
-    x = np.zeros((L, d)) if x_in is None else np.array(x_in, dtype=np.float64)
-    p = np.zeros((L, T)); q = np.zeros((a.shape[0], L, T))
-    for t in range(T):
-        xp = np.einsum("lij,lj->li", A, x)
-        p[:, t] = xp[:, 0]
-        y = Ty[:, t]
-        x = xp + K * np.where(np.isnan(y), 0.0, y - p[:, t])[:, None]
-        q[:, :, t] = np.einsum("kld,ld->kl", a, x)
-    p, q = r32(p), r32(q)
-    v = r32(np.where(np.isnan(Ty), 0.0, Ty - p))
-    s = np.zeros((L, d)); ys = np.zeros((L, T))
-    for t in range(T - 1, -1, -1):
-        q[:, :, t] += np.einsum("kld,ld->kl", g, s)
-        s = np.einsum("lij,lj->li", G, s) + K * v[:, t:t + 1]
-        ys[:, t] = r32(p[:, t] + r32(s[:, 0]))
-    return r32(q), ys, r32(x)
-
-
-def slope_np(tbs, F_list, dt, fracs, Ty, x_in=None, given="all", emulate32=False):
-    """Returns (slope [K][L][T], ys [L][T], the end state [L][d], var [K][L])."""
-    rows = [[slope_rows_np(tb, F, dt, phi, given) for tb, F in zip(tbs, F_list)] for phi in fracs]
-    a = np.array([[r[0] for r in rk] for rk in rows]); g = np.array([[r[1] for r in rk] for rk in rows])     # [K][L][d]
-    planes, ys, x = sweeps_np(tbs, a, g, Ty, x_in, emulate32)
-    return planes, ys, x, np.array([[r[2] for r in rk] for rk in rows])
 
 
 def dense_slope(tb, F, dt, y, n, ticks, past=False):
@@ -234,33 +191,16 @@ def test_numpy_slope_is_the_central_difference_of_the_off_grid_mean(kern):
 
 
 def test_header_and_loader_declare_the_slope_entries():
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "moihgp.h")).read(), flags=re.S)
-    from multioutputihgp_amd import _lib
-    for n in SLOPE_SYMBOLS:
-        assert re.search(r"\b%s\s*\(" % n, src), n
-        assert n in _lib.ADDITIVE_SYMBOLS, n
+    src = assert_declared(SLOPE_SYMBOLS)
     assert re.search(r"#define\s+MOIHGP_SLOPE_ALL\s+0\b", src) and re.search(r"#define\s+MOIHGP_SLOPE_PAST\s+1\b", src)
 
 
 def test_library_exports_the_slope_entries(hip_built):
-    lib = C.CDLL(hip_built)
-    for n in SLOPE_SYMBOLS:
-        assert hasattr(lib, n), n
-
-
-def _cxx_slope(hip_built):
-    import subprocess
-    build = os.path.join(ROOT, "build", "cxx_tests")
-    os.makedirs(build, exist_ok=True)
-    exe = os.path.join(build, "slope_test")
-    libdir = os.path.dirname(hip_built)
-    subprocess.run(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cxx", "slope_test.cpp"),
-                    "-o", exe, "-L", libdir, "-lmoihgp", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    return exe
+    assert_exported(hip_built, SLOPE_SYMBOLS)
 
 
 def test_cxx_predict_slope_compiles_and_links(hip_built):
-    assert os.path.exists(_cxx_slope(hip_built))
+    assert os.path.exists(cxx_test_binary(hip_built, "slope_test"))
 
 
 def test_python_argument_validation():
@@ -294,7 +234,7 @@ def parity_case(kern, L, T):
         tbs, Fs = pool_models(kern, L)
         Ty = synth(L, T, rng)
         if T >= 16:
-            Ty = with_gaps(Ty, rng)
+            Ty = gaps_edges_inplace(Ty, rng)
         Ty = Ty.astype(np.float32).astype(np.float64)
         x0 = (0.1 * rng.standard_normal((L, Fs[0].shape[0]))).astype(np.float32).astype(np.float64)
         sets = frac_sets(L)
@@ -334,15 +274,6 @@ def test_fp32_emulation_stays_below_its_figures():
 
 
 # ------------------------------------------------------------------------------------------------ GPU
-@pytest.fixture(scope="module")
-def env(hip_built):
-    import torch
-    assert torch.cuda.is_available(), "GPU suite needs a GPU"
-    torch.cuda.set_device(0)
-    from multioutputihgp_amd import streams
-    return dict(torch=torch, streams=streams)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("kern", KERNS)
 @pytest.mark.parametrize("L", PARITY_L)
@@ -373,11 +304,11 @@ def test_slope_parity(env, kern, L, T, dtype, given):
         errs = [rel_err_rows(got[k], want["ref"][name][k]) for k in range(K)]
         ex = rel_err_rows(x.double().cpu().numpy(), want["xe"], floor=1e-3)
         print(f"{kern} {dtype} {given} L={L} T={T} fracs={fracs}: planes {['%.1e' % e for e in errs]}, end state {ex:.1e}")
-        assert max(errs) <= tol_of(dtype), errs
-        assert ex <= tol_of(dtype), ex
+        assert max(errs) <= slope_tol_of(dtype), errs
+        assert ex <= slope_tol_of(dtype), ex
         if given == "all":
             ey = rel_err_rows(ys.double().cpu().numpy(), want["ys"])
-            assert ey <= tol_of(dtype, ysmooth=True), ey
+            assert ey <= slope_tol_of(dtype, ysmooth=True), ey
             assert ys.data_ptr() == ysm.data_ptr()
         else:
             assert ys is None
@@ -453,10 +384,10 @@ def test_scan_and_serial_paths_agree(env, kern, given, dtype):
         res.append((s.double().cpu().numpy(), x.double().cpu().numpy()))
     ref = case[given]["ref"]["3"]
     for k in range(3):
-        assert rel_err_rows(res[0][0][k], res[1][0][k]) <= tol_of(dtype)
+        assert rel_err_rows(res[0][0][k], res[1][0][k]) <= slope_tol_of(dtype)
         for path in (0, 1):
-            assert rel_err_rows(res[path][0][k], ref[k]) <= tol_of(dtype)
-    assert rel_err_rows(res[0][1], res[1][1], floor=1e-3) <= tol_of(dtype)
+            assert rel_err_rows(res[path][0][k], ref[k]) <= slope_tol_of(dtype)
+    assert rel_err_rows(res[0][1], res[1][1], floor=1e-3) <= slope_tol_of(dtype)
 
 
 @pytest.mark.gpu
@@ -607,18 +538,8 @@ def test_calls_on_two_streams_keep_their_own_tables(env):
 
 
 def _slope_outputs_np(gp, Y, kern, fracs, given):
-    M, L = gp.num_output, gp.num_latent
-    prm = gp.params
-    U, S = prm[:M * L].reshape(M, L), prm[M * L:M * L + L]
-    igp = prm[-3 * L:].reshape(L, 3)
-    Ty = np.zeros((L, Y.shape[0]))
-    for t, y in enumerate(Y):
-        obs = ~np.isnan(y)
-        if obs.sum() < L:
-            Ty[:, t] = np.nan
-            continue
-        U0 = U[obs]
-        Ty[:, t] = np.linalg.solve(U0.T @ U0, U0.T @ y[obs]) / np.sqrt(S)
+    U, S, igp, Ty = project_np(gp, Y, nan_below_L=True)
+    L = len(igp)
     tbs = [tables(kern, DT, igp[l]) for l in range(L)]
     slope, _, _, var = slope_np(tbs, [F_of(kern, DT, igp[l]) for l in range(L)], DT, fracs, Ty, given=given)
     return np.einsum("ml,klt->ktm", U * np.sqrt(S), slope), (S[None, :] * var) @ (U ** 2).T
@@ -633,7 +554,7 @@ def test_slope_outputs_end_to_end(env, kern, missing, given):
     from multioutputihgp_amd import MOIHGP
     rng = np.random.default_rng(27)
     M, L, T, fracs = 12, 4, 600, [0.0, 0.5]
-    params, Y = _end_to_end_inputs(rng, M, L, T, missing)
+    params, Y = end_to_end_inputs(rng, M, L, T, missing)
     gp = MOIHGP(DT, M, L, kernel=KMAP[kern])
     gp.update(params)
     dY, var_dY = streams.slope_outputs(gp, torch.from_numpy(Y).cuda(), fracs, given)
@@ -667,22 +588,20 @@ def test_slope_outputs_raises_on_a_failed_latent(env):
 @pytest.mark.gpu
 @pytest.mark.parametrize("kern", KERNS)
 def test_cxx_predict_slope_matches_python(env, hip_built, kern):
-    import subprocess
     torch, streams = env["torch"], env["streams"]
     from multioutputihgp_amd import MOIHGP
     rng = np.random.default_rng(28)
     M, L, T, frac = 12, 4, 300, 0.375
-    params, Y = _end_to_end_inputs(rng, M, L, T, True)
-    fmt = lambda a: " ".join("nan" if np.isnan(v) else repr(float(v)) for v in np.ravel(a))
-    exe = _cxx_slope(hip_built)
+    params, Y = end_to_end_inputs(rng, M, L, T, True)
+    exe = cxx_test_binary(hip_built, "slope_test")
 
     def run(fr, past):
-        inp = f"{0 if kern == 'Matern32' else 1} {M} {L} 0.1 {fr!r} {past} {T}\n{fmt(params)}\n" + "\n".join(fmt(y) for y in Y) + "\n"
-        return subprocess.run([exe], input=inp, capture_output=True, text=True, check=True).stdout.strip().split("\n")
+        inp = f"{0 if kern == 'Matern32' else 1} {M} {L} 0.1 {fr!r} {past} {T}\n{cxx_fmt(params)}\n" + "\n".join(cxx_fmt(y) for y in Y) + "\n"
+        return cxx_run(exe, inp)
     gp = MOIHGP(DT, M, L, kernel=KMAP[kern])
     gp.update(params)
     for past, given in ((0, "all"), (1, "past")):
-        got = np.array([[float(v) for v in line.split()] for line in run(frac, past)])
+        got = cxx_rows(run(frac, past))
         dY, _ = streams.slope_outputs(gp, torch.from_numpy(Y).cuda(), [frac], given)
         torch.cuda.synchronize()
         assert got.shape == (T, M)

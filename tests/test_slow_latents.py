@@ -1,6 +1,6 @@
 """The stream sweeps (smooth, forecast, lagged, forecast_tail and the two variance tables) on latents that decay slowly.
 
-The other stream tests draw every latent from test_smoother.POOL (lengthscales 0.5 .. 2.0 at dt = 0.1): anything further than a few hundred ticks
+The other stream tests draw every latent from stream_support.POOL (lengthscales 0.5 .. 2.0 at dt = 0.1): anything further than a few hundred ticks
 away has decayed to nothing there, so a forecast plane at h = 300, a lag of 1023 or the far blocks of a tail of 4096 are compared against numbers
 far below any tolerance.  Three slow rows (magnitude, lengthscale, noise variance), mixed into a bank with POOL rows so that no slow row is alone
 in a launch, keep those parts of the kernels above it:
@@ -29,13 +29,14 @@ import numpy as np
 import pytest
 
 from conftest import rel_err_rows
-from test_forecast import HMAX, forecast_np, forecast_var_np, gain_tables, make_bank, padding_untouched, plane_err, sentinel_out, tol_of
-from test_lagged import LAGS8, LMAX, forward_np, lagged_np, lagged_var_np, with_gaps
-from test_smoother import POOL, bank_and_tables, smooth_np, synth, tables, to_dev
+from parity_support import synth
+from stream_reference import forecast_np, forecast_var_np, forward_np, gain_tables, lagged_np, lagged_var_np, smooth_np, tables
+from stream_support import (HMAX, LAGS8, LMAX, POOL, bank_and_tables, env, gaps_edges_blocks_inplace, make_bank, padding_untouched, plane_err,
+                            round32, sentinel_out, tdt_of, to_dev, tol_of)  # noqa: F401  (env: the module's fixture)
 
 SLOW = [(1.0, 50.0, 0.1), (0.8, 200.0, 0.1), (1.2, 100.0, 0.02)]
 FAR_PRM = SLOW[1]
-# the bank: the slow rows first, the slowest on an even row (with_gaps blanks ticks 1024 .. 2047 of the odd rows, which would leave it nothing to
+# the bank: the slow rows first, the slowest on an even row (gaps_edges_blocks_inplace blanks ticks 1024 .. 2047 of the odd rows, which would leave it nothing to
 # tell lag 1023 from the smoother by), then four POOL rows, the R = 1e-6 one among them
 BANK = [SLOW[0], SLOW[2], SLOW[1], POOL[3], POOL[0], POOL[1], POOL[4]]
 L = len(BANK)
@@ -55,10 +56,6 @@ VAR_LAGS = [0, 1, 16, 300]
 QUALIFY = 1e-3                                           # a plane / block / variance term is held against its own size from here up
 HANDLE_TABLE_TOL = 1e-5                                  # the handle's literal tables on the slow rows: thirty times their measured own error
 F32_INPUT_BOUND = 3e-4                                 # half a decade under FP32_TOL, as tests/test_parameter_box.py keeps
-
-
-def _round32(a):
-    return np.asarray(a, dtype=np.float64).astype(np.float32).astype(np.float64)
 
 
 def _norm_inf(X):
@@ -88,13 +85,13 @@ def start_state(kern, rng, size):
     weigh them by ~(h dt)^i) would then exceed the h = 0 scale the planes are measured against by three decades on the short streams."""
     d = 2 if kern == "Matern32" else 3
     lam = np.array([np.sqrt(2 * d - 1) / p[1] for p in BANK])
-    return _round32(size * rng.standard_normal((L, d)) * lam[:, None] ** np.arange(d)[None, :])
+    return round32(size * rng.standard_normal((L, d)) * lam[:, None] ** np.arange(d)[None, :])
 
 
 def _stream(T, rng, variant):
     Ty = synth(L, T, rng)
     if variant != "dense":
-        Ty = with_gaps(Ty, rng)
+        Ty = gaps_edges_blocks_inplace(Ty, rng)
     return Ty
 
 
@@ -108,7 +105,7 @@ def forecast_case(kern, gains, T, variant):
     Ty = _stream(T, rng, variant)
     if variant == "gaps":
         Ty[NAN_ROW] = np.nan
-    Ty = _round32(Ty)
+    Ty = round32(Ty)
     x0 = start_state(kern, rng, 0.1)
     ref, xe, scale = forecast_np(tbs, Ty, FC_HORIZONS, x0)
     own = np.max(np.abs(ref), axis=-1)
@@ -138,7 +135,7 @@ def forecast_f32_np(tbs, Ty, horizons, x0):
 def smooth_case(kern, T, variant):
     rng = np.random.default_rng([("Matern32", "Matern52").index(kern), T, ("dense", "gaps").index(variant), 42])
     tbs = list(bank_tables(kern))
-    Ty = _round32(_stream(T, rng, variant))
+    Ty = round32(_stream(T, rng, variant))
     x0 = start_state(kern, rng, 0.1)
     ref, xe = smooth_np(tbs, Ty, x0)
     return dict(Ty=Ty, x0=x0, ref=ref, xe=xe)
@@ -148,7 +145,7 @@ def smooth_case(kern, T, variant):
 def lagged_case(kern, T):
     rng = np.random.default_rng([("Matern32", "Matern52").index(kern), T, 43])
     tbs = list(bank_tables(kern))
-    Ty = _round32(_stream(T, rng, "gaps"))
+    Ty = round32(_stream(T, rng, "gaps"))
     x0 = start_state(kern, rng, 0.1)
     ref, p, xe = lagged_np(tbs, Ty, LAGS8 + LAGS2, x0)
     return dict(Ty=Ty, x0=x0, p=p, xe=xe, ref={"8": ref[:8], "2": ref[8:]})
@@ -296,19 +293,6 @@ def test_tail_reaches_every_block(kern):
 
 
 # ------------------------------------------------------------------------------------------------ GPU
-@pytest.fixture(scope="module")
-def env(hip_built):
-    import torch
-    assert torch.cuda.is_available(), "GPU suite needs a GPU"
-    torch.cuda.set_device(0)
-    from multioutputihgp_amd import streams
-    return dict(torch=torch, streams=streams)
-
-
-def _tdt(torch, dtype):
-    return torch.float64 if dtype == "f64" else torch.float32
-
-
 _HANDLE_CASES = {}
 
 
@@ -336,7 +320,7 @@ def _handle_case_on_device_tables(bank, tbs, case, kern, T, variant):
 
 def _run_forecast(env, kern, gains, T, dtype, variant, K=8, alias=False):
     torch, streams = env["torch"], env["streams"]
-    tdt = _tdt(torch, dtype)
+    tdt = tdt_of(torch, dtype)
     case = forecast_case(kern, gains, T, variant)
     hs = FC_HORIZONS[:K]
     bank, tbs, _ = make_bank(streams, kern, L, gains, pool=BANK)
@@ -371,7 +355,7 @@ def _run_forecast(env, kern, gains, T, dtype, variant, K=8, alias=False):
 @pytest.mark.parametrize("T", TS)
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
 def test_forecast_parity(env, kern, gains, T, dtype, variant):
-    """Dense streams (whole wavefronts on the branch without selects) and with_gaps ones with one row entirely missing, K = 8 horizons out to
+    """Dense streams (whole wavefronts on the branch without selects) and gapped ones (gaps_edges_blocks_inplace) with one row entirely missing, K = 8 horizons out to
     4096 and HMAX: every plane against the h = 0 scale, and every qualifying plane of a latent against its own maximum."""
     _run_forecast(env, kern, gains, T, dtype, variant)
 
@@ -391,7 +375,7 @@ def test_forecast_parity_seven_horizons(env, dtype):
 
 def _run_smooth(env, kern, T, dtype, variant, alias=False):
     torch, streams = env["torch"], env["streams"]
-    tdt = _tdt(torch, dtype)
+    tdt = tdt_of(torch, dtype)
     case = smooth_case(kern, T, variant)
     bank, _, _ = bank_and_tables(streams, kern, L, pool=BANK)
     x_start = torch.from_numpy(case["x0"]).to(tdt).cuda()
@@ -431,10 +415,10 @@ def test_smooth_parity_x_aliases_x_start(env, kern):
 @pytest.mark.parametrize("T", LAG_TS)
 @pytest.mark.parametrize("dtype", ["f64", "f32"])
 def test_lagged_parity(env, kern, T, dtype):
-    """LAGS8 and [300, 40] on with_gaps streams of 2049 and 2100 ticks.  At fp64 the planes of lags 1023 and 1024 differ from the smoothed mean
+    """LAGS8 and [300, 40] on gapped streams (gaps_edges_blocks_inplace) of 2049 and 2100 ticks.  At fp64 the planes of lags 1023 and 1024 differ from the smoothed mean
     and from each other by far more than the tolerance on (0.8, 200, 0.1); at fp32 the lag-300 plane does."""
     torch, streams = env["torch"], env["streams"]
-    tdt = _tdt(torch, dtype)
+    tdt = tdt_of(torch, dtype)
     case = lagged_case(kern, T)
     bank, _, _ = bank_and_tables(streams, kern, L, pool=BANK)
     dev = to_dev(torch, case["Ty"], tdt, T)
@@ -465,7 +449,7 @@ def test_lagged_parity(env, kern, T, dtype):
 def test_lagged_state_at_chunk_and_segment_edges(env, kern, dtype, path):
     """The filtered state after tick state_at - 1, with state_at on a chunk edge, a segment edge and one tick either side of each."""
     torch, streams = env["torch"], env["streams"]
-    tdt = _tdt(torch, dtype)
+    tdt = tdt_of(torch, dtype)
     T = 2100
     case = lagged_case(kern, T)
     tbs = list(bank_tables(kern))
@@ -492,7 +476,7 @@ def test_tail(env, kern, dtype):
     """forecast_tail from a state with derivative components: per row as test_forecast.test_tail, and per 1024-block (one workgroup each) against
     the block's own maximum on the rows where the block reaches QUALIFY of the row maximum."""
     torch, streams = env["torch"], env["streams"]
-    tdt = _tdt(torch, dtype)
+    tdt = tdt_of(torch, dtype)
     case = tail_case(kern)
     bank, _, _ = make_bank(streams, kern, L, "kalman", pool=BANK)
     xd = torch.from_numpy(case["x0"]).to(tdt).cuda()

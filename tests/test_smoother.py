@@ -2,68 +2,20 @@
 RTS loop, the dense GP posterior and scipy's Kalman DARE (CPU), then the library's tables and sweeps against it (GPU)."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
-import scipy.linalg as sl
 
-from conftest import ROOT, rel_err, rel_err_rows
-from oracle.moihgp_numpy import IHGP
+from conftest import rel_err, rel_err_rows
+from parity_support import synth
+from stream_reference import smooth_np, smooth_outputs_np, tables
+from stream_support import (CASES, KMAP, POOL, assert_declared, assert_exported, bank_and_tables, cxx_fmt, cxx_rows, cxx_run, cxx_test_binary,
+                            end_to_end_inputs, env, to_dev)  # noqa: F401  (env: the module's fixture)
 
 SMOOTH_SYMBOLS = ("moihgp_smooth_stream", "moihgp_get_smoother", "moihgp_latent_variances")
-KMAP = {"Matern32": "Matern32", "Matern52": "Matern52ss"}
 
 
-# ------------------------------------------------------------------------------------------------ numpy definition
-def model(kern, dt, prm):
-    g = IHGP(dt, kern)
-    g.update(np.asarray(prm, dtype=np.float64))
-    A, Pinf = g.A, g.ss.Pinf
-    Q = Pinf - A @ Pinf @ A.T
-    return A, (Q + Q.T) / 2.0, float(prm[2]), Pinf
-
-
-def tables(kern, dt, prm):
-    """Kalman DARE (scipy), K, G = PF A^T P^-1, Ps from the d^2 x d^2 Stein system; None where scipy's solver fails (its residual)."""
-    A, Q, R, Pinf = model(kern, dt, prm)
-    d = A.shape[0]
-    H = np.zeros((1, d)); H[0, 0] = 1.0
-    try:
-        P = sl.solve_discrete_are(A.T, H.T, Q, np.array([[R]]))
-    except (np.linalg.LinAlgError, ValueError):
-        return None
-    res = A @ P @ A.T - np.outer(A @ P[:, 0], A @ P[:, 0]) / (P[0, 0] + R) + Q - P
-    if not np.all(np.isfinite(P)) or np.max(np.abs(res)) > 1e-10 * np.max(np.abs(P)):
-        return None
-    S = P[0, 0] + R
-    K = P[:, 0] / S
-    PF = P - np.outer(K, P[0])
-    G = PF @ A.T @ np.linalg.inv(P)
-    Ps = np.linalg.solve(np.eye(d * d) - np.kron(G, G), (PF - G @ P @ G.T).ravel()).reshape(d, d)
-    return dict(A=A, Q=Q, R=R, Pinf=Pinf, P=P, S=S, K=K, PF=PF, G=G, Ps=(Ps + Ps.T) / 2, var_f=PF[0, 0], var_s=Ps[0, 0])
-
-
-def smooth_np(tbs, Ty, x_in=None):
-    """The two sweeps of include/moihgp.h, vectorised over latents: tbs one table dict per row of Ty [L][T]."""
-    A = np.stack([t["A"] for t in tbs]); K = np.stack([t["K"] for t in tbs]); G = np.stack([t["G"] for t in tbs])
-    L, T = Ty.shape
-    d = A.shape[1]
-    x = np.zeros((L, d)) if x_in is None else np.array(x_in, dtype=np.float64)
-    p = np.zeros((L, T)); v = np.zeros((L, T))
-    for t in range(T):
-        xp = np.einsum("lij,lj->li", A, x)
-        p[:, t] = xp[:, 0]
-        y = Ty[:, t]
-        v[:, t] = np.where(np.isnan(y), 0.0, y - p[:, t])
-        x = xp + K * v[:, t:t + 1]
-    s = np.zeros((L, d)); ys = np.zeros((L, T))
-    for t in range(T - 1, -1, -1):
-        s = np.einsum("lij,lj->li", G, s) + K * v[:, t:t + 1]
-        ys[:, t] = p[:, t] + s[:, 0]
-    return ys, x
-
-
+# ------------------------------------------------------------------------------------------------ cross-checks of the numpy definition
 def rts_textbook(tb, y):
     A, K, G = tb["A"], tb["K"], tb["G"]
     x = np.zeros(A.shape[0]); xf = []
@@ -92,17 +44,11 @@ def dense_posterior(tb, y):
 
 # ------------------------------------------------------------------------------------------------ CPU
 def test_header_and_loader_declare_the_smoother():
-    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "moihgp.h")).read(), flags=re.S)
-    from multioutputihgp_amd import _lib
-    for n in SMOOTH_SYMBOLS:
-        assert re.search(r"\b%s\s*\(" % n, src), n
-        assert n in _lib.ADDITIVE_SYMBOLS, n
+    assert_declared(SMOOTH_SYMBOLS)
 
 
 def test_library_exports_the_smoother(hip_built):
-    lib = C.CDLL(hip_built)
-    for n in SMOOTH_SYMBOLS:
-        assert hasattr(lib, n), n
+    assert_exported(hip_built, SMOOTH_SYMBOLS)
 
 
 @pytest.mark.parametrize("kern", ["Matern32", "Matern52"])
@@ -143,37 +89,6 @@ def test_smoother_gain_is_contractive_over_the_learners_box():
 
 
 # ------------------------------------------------------------------------------------------------ GPU
-POOL = [(1.0, 1.0, 0.1), (0.5, 0.6, 0.02), (2.0, 1.7, 0.3), (1.3, 0.8, 1e-6), (0.8, 2.0, 0.05), (1.6, 0.5, 0.2), (0.7, 1.2, 0.01), (1.1, 0.9, 1e-3)]
-
-
-def bank_and_tables(streams, kern, L, dt=0.1, pool=POOL):
-    prm = np.array([pool[l % len(pool)] for l in range(L)], dtype=np.float64)
-    tbs = {}
-    for p in pool:
-        tbs[p] = tables(kern, dt, p)
-    return streams.LatentBank(dt, prm, kernel=KMAP[kern]), [tbs[pool[l % len(pool)]] for l in range(L)], prm
-
-
-def synth(L, T, rng):
-    t = np.arange(T)[None, :]; l = np.arange(L)[:, None]
-    return np.sin(0.05 * t * (1 + l % 7)) + 0.1 * rng.standard_normal((L, T))
-
-
-@pytest.fixture(scope="module")
-def env(hip_built):
-    import torch
-    assert torch.cuda.is_available(), "GPU suite needs a GPU"
-    torch.cuda.set_device(0)
-    from multioutputihgp_amd import streams
-    return dict(torch=torch, streams=streams)
-
-
-def to_dev(torch, a, dtype, T):
-    buf = torch.full((a.shape[0], (T + 3) // 4 * 4 + 4), float("nan"), dtype=dtype, device="cuda")
-    buf[:, :T] = torch.from_numpy(a).to(dtype)
-    return buf[:, :T]
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("kern", ["Matern32", "Matern52"])
 def test_tables_match_scipy(env, kern):
@@ -221,9 +136,6 @@ def test_stacked_model_returns_3(env):
     assert lib.moihgp_latent_variances(bank._h, None, None) == 3
     with pytest.raises(MoihgpError):
         bank.smooth(Ty)
-
-
-CASES = [(L, T) for L in (1, 7, 256) for T in (1, 2, 63, 1000, 10037)] + [(4096, 63), (4096, 1000)]
 
 
 @pytest.mark.gpu
@@ -294,21 +206,6 @@ def test_interior_is_the_gp_posterior_on_the_device(env):
     assert abs(bank.smoother(0)["var_smoothed"] - var[750]) <= 1e-9
 
 
-def _smooth_outputs_np(gp, Y, kern):
-    M, L = gp.num_output, gp.num_latent
-    prm = gp.params
-    U, S = prm[:M * L].reshape(M, L), prm[M * L:M * L + L]
-    igp = prm[-3 * L:].reshape(L, 3)
-    Ty = np.zeros((L, Y.shape[0]))
-    for t, y in enumerate(Y):
-        obs = ~np.isnan(y)
-        U0 = U[obs]
-        Ty[:, t] = np.linalg.solve(U0.T @ U0, U0.T @ y[obs]) / np.sqrt(S)
-    tbs = [tables(kern, 0.1, igp[l]) for l in range(L)]
-    ys, _ = smooth_np(tbs, Ty)
-    return (U * np.sqrt(S)) @ ys, (U ** 2) @ (S * np.array([t["var_s"] for t in tbs]))
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("missing", [False, True])
 def test_smooth_outputs_end_to_end(env, missing):
@@ -317,15 +214,11 @@ def test_smooth_outputs_end_to_end(env, missing):
     rng = np.random.default_rng(7)
     M, L, T = 64, 16, 2000
     gp = MOIHGP(0.1, M, L, kernel="Matern52ss")
-    params = np.concatenate([(np.eye(M, L) + 0.2 * rng.standard_normal((M, L))).ravel(), rng.uniform(0.5, 2, L), [0.05],
-                             np.column_stack([rng.uniform(0.5, 2, L), rng.uniform(0.5, 2, L), rng.uniform(0.05, 0.2, L)]).ravel()])
+    params, Y = end_to_end_inputs(rng, M, L, T, missing)
     gp.update(params)
-    Y = np.sin(0.02 * np.arange(T)[:, None] * (1 + np.arange(M)[None, :] % 5)) + 0.1 * rng.standard_normal((T, M))
-    if missing:
-        Y[rng.random((T, M)) < 0.02] = np.nan
     Ys, var = streams.smooth_outputs(gp, torch.from_numpy(Y).cuda())
     torch.cuda.synchronize()
-    ref, vref = _smooth_outputs_np(gp, Y, "Matern52")
+    ref, vref = smooth_outputs_np(gp, Y, "Matern52")
     assert rel_err(Ys.T.cpu().numpy(), ref) <= 1e-9
     assert rel_err(var, vref) <= 1e-10
 
@@ -349,37 +242,21 @@ def test_full_size_c3_fp32_sampled(env):
 
 
 # ------------------------------------------------------------------------------------------------ C++ (predictSmoothed)
-def _cxx_smoother(hip_built):
-    import subprocess
-    build = os.path.join(ROOT, "build", "cxx_tests")
-    os.makedirs(build, exist_ok=True)
-    exe = os.path.join(build, "smoother_test")
-    libdir = os.path.dirname(hip_built)
-    subprocess.run(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cxx", "smoother_test.cpp"),
-                    "-o", exe, "-L", libdir, "-lmoihgp", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    return exe
-
-
 def test_cxx_predict_smoothed_compiles_and_links(hip_built):
-    assert os.path.exists(_cxx_smoother(hip_built))
+    assert os.path.exists(cxx_test_binary(hip_built, "smoother_test"))
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("kern", ["Matern32", "Matern52"])
 def test_cxx_predict_smoothed_matches_python(env, hip_built, kern):
-    import subprocess
     torch, streams = env["torch"], env["streams"]
     from multioutputihgp_amd import MOIHGP
     rng = np.random.default_rng(10)
     M, L, T = 12, 4, 300
-    params = np.concatenate([(np.eye(M, L) + 0.2 * rng.standard_normal((M, L))).ravel(), rng.uniform(0.5, 2, L), [0.05],
-                             np.column_stack([rng.uniform(0.5, 2, L), rng.uniform(0.5, 2, L), rng.uniform(0.05, 0.2, L)]).ravel()])
-    Y = np.sin(0.02 * np.arange(T)[:, None] * (1 + np.arange(M)[None, :] % 5)) + 0.1 * rng.standard_normal((T, M))
-    Y[rng.random((T, M)) < 0.02] = np.nan
-    fmt = lambda a: " ".join("nan" if np.isnan(v) else repr(float(v)) for v in np.ravel(a))
-    inp = f"{0 if kern == 'Matern32' else 1} {M} {L} 0.1 {T}\n{fmt(params)}\n" + "\n".join(fmt(y) for y in Y) + "\n"
-    out = subprocess.run([_cxx_smoother(hip_built)], input=inp, capture_output=True, text=True, check=True).stdout.strip().split("\n")
-    got = np.array([[float(v) for v in line.split()] for line in out])
+    params, Y = end_to_end_inputs(rng, M, L, T, True)
+    inp = f"{0 if kern == 'Matern32' else 1} {M} {L} 0.1 {T}\n{cxx_fmt(params)}\n" + "\n".join(cxx_fmt(y) for y in Y) + "\n"
+    out = cxx_run(cxx_test_binary(hip_built, "smoother_test"), inp)
+    got = cxx_rows(out)
     gp = MOIHGP(0.1, M, L, kernel=KMAP[kern])
     gp.update(params)
     Ys, _ = streams.smooth_outputs(gp, torch.from_numpy(Y).cuda())

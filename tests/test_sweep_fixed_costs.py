@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from conftest import rel_err, rel_err_rows
-from test_gpu_parity import FP32_TOL, FP64_TIGHT, KMAP, env, synth, synth_params, to_dev  # noqa: F401  (env: fixture)
+from parity_support import FP32_TOL, FP64_TIGHT, KMAP, env, synth, synth_params, to_dev  # noqa: F401  (env: fixture)
 
 pytestmark = pytest.mark.gpu
 

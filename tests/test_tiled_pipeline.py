@@ -13,8 +13,8 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, rel_err
+from stream_support import KMAP, cxx_test_binary
 
-KMAP = {"Matern32": "Matern32", "Matern52": "Matern52ss"}
 NEW_SYMBOLS = ("moihgp_project_stream_tiled", "moihgp_unproject_stream_tiled")
 SHAPES = [(3, 1), (101, 70), (96, 64), (260, 130)]      # (M, L): one latent; odd ldb, scalar loads; vector loads; a partial second row tile
 SENTINEL = 12345.0
@@ -45,18 +45,8 @@ def test_library_exports_the_tiled_products(hip_built):
         assert getattr(loaded, name).argtypes is not None and len(getattr(loaded, name).argtypes) == 6
 
 
-def _cxx_predict_stream(hip_built):
-    build = os.path.join(ROOT, "build", "cxx_tests")
-    os.makedirs(build, exist_ok=True)
-    exe = os.path.join(build, "predict_stream_test")
-    libdir = os.path.dirname(hip_built)
-    subprocess.run(["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cxx", "predict_stream_test.cpp"),
-                    "-o", exe, "-L", libdir, "-lmoihgp", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"], check=True)
-    return exe
-
-
 def test_cxx_predict_stream_compiles_and_links(hip_built):
-    assert os.path.exists(_cxx_predict_stream(hip_built))
+    assert os.path.exists(cxx_test_binary(hip_built, "predict_stream_test"))
 
 
 # ------------------------------------------------------------------------------------------------ GPU
@@ -396,7 +386,7 @@ def test_cxx_predict_stream_matches_python(env, hip_built, kern, tiled):
     Y[rng.random((T, M)) < 0.02] = np.nan
     fmt = lambda a: " ".join("nan" if np.isnan(v) else repr(float(v)) for v in np.ravel(a))
     inp = f"{0 if kern == 'Matern32' else 1} {M} {L} 0.1 {T} {tiled}\n{fmt(params)}\n" + "\n".join(fmt(y) for y in Y) + "\n"
-    out = subprocess.run([_cxx_predict_stream(hip_built)], input=inp, capture_output=True, text=True, check=True).stdout.strip().split("\n")
+    out = subprocess.run([cxx_test_binary(hip_built, "predict_stream_test")], input=inp, capture_output=True, text=True, check=True).stdout.strip().split("\n")
     got = np.array([[float(v) for v in line.split()] for line in out])
     gp = env["MOIHGP"](0.1, M, L, kernel=KMAP[kern])
     gp.update(params)

@@ -6,7 +6,7 @@ os.environ["MOIHGP_GAP_TRACE"] = "1"
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 import numpy as np, torch
-import test_gpu_parity as tp
+import parity_support as tp
 from multioutputihgp_amd import streams
 from oracle import cref
 kern, L, T, nanf, dt_, seed = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), float(sys.argv[4]), sys.argv[5], int(sys.argv[6])
