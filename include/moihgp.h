@@ -484,6 +484,46 @@ int moihgp_sample_noise(unsigned long long seed, unsigned latent0, size_t L, uns
                         float* noise, size_t ld, float* start, void* stream);
 int moihgp_get_sampler(moihgp_gp* gp, size_t l, double* B, double* sigma2, double* Sigma, double* Lc, double* acov_err, int* status);
 
+/* ---- seeded forecast paths: joint draws of the ticks beyond a stream (not in the reference) ------------------------------------------------------
+ * moihgp_forecast_tail gives the means past the end of a stream and moihgp_forecast_variances the variance of every horizon; neither says how the
+ * horizons vary together (the sum over the next n ticks, the largest of them, a set of scenarios).  These are whole trajectories whose covariance
+ * across horizons is the GP predictive one.  The textbook recursion x <- A x + chol(Q) n does not exist for these models: the reference's
+ * Matern-5/2 makes Q = Pinf - A Pinf A^T indefinite.  The innovations form of the steady-state predictor is always valid: one scalar normal per
+ * tick with variance Sv = P_00 + R > 0.  It draws what will be OBSERVED (the latent's projected observation, noise included): the quantity
+ * moihgp_forecast_scores scores, with pvar its variance.
+ * Per latent, with the handle's A, the smoother's K and P (moihgp_get_smoother), the noise parameter R and Sv = P_00 + R; per sample s, with u[-1]
+ * the start state and q = step0 + j the absolute step index, for j = 0 .. n-1 (fp64 arithmetic for both stream types, rounded once at the store):
+ *     e = sqrt(Sv) n[q];    u[j] = A u[j-1] + K e;    paths[s][l][j] = u[j]_0 + (1 - K_0) e
+ * i.e. the one-step predicted mean (A u[j-1])_0 plus the innovation e, the filtered state then carried on as if paths[s][l][j] had been observed.
+ * states_out[s][l] = u[n-1] (the start state when n = 0).
+ * Noise: Philox4x32-10 exactly as the sampler's (the same key, Box-Muller in fp32), counter = (q / 4, latent0 + l, sample0 + s, tag 2), element
+ * q % 4; tags 0 and 1 are the sampler's, so the draws inside a stream and the draws of its future are independent for one seed.  Nothing of the
+ * noise is stored.
+ * What the draws are: their mean over draws is H A^{j+1} x (moihgp_forecast_tail); their covariance is C = Sv Lam Lam^T with Lam lower-triangular
+ * Toeplitz, taps lam_0 = 1, lam_k = (A^k K)_0 -- the GP predictive covariance of y[T .. T+n) given a long past -- and
+ * C_jj = moihgp_forecast_variances([j+1]) + R.  They are draws given the data up to the end state and nothing else: they are NOT jointly consistent
+ * with a moihgp_sample_stream draw of the same stream.  Un-projected through the mixing (moihgp_unproject_stream per plane) they are draws of the
+ * outputs' observation process inside the mixing's span, with the latents' noise; the sigma^2 component outside the span is not drawn.
+ * Not offered: draws of the noise-free function ahead (no recursive realization without a positive semi-definite Q); stacked models (return 3, as
+ * everywhere else); a time-parallel scan (a horizon is short next to a stream and the parallelism is in the S L rows: one lane walks one row).
+ * moihgp_forecast_paths: exactly one of x ([L][d], dtype, the start of every sample: a stream's end state) and states_in ([S][L][d], fp64 DEVICE:
+ *   the states_out of an earlier call) is non-NULL.  states_out [S][L][d] fp64 DEVICE or NULL; it may equal states_in.  n <= 2^20,
+ *   step0 + n <= 2^32, nsamples 1 .. 65535.  paths [S][L][ld_out] (dtype), plane s starting s * plane_stride elements after paths; strides and
+ *   alignment as moihgp_forecast_stream's fc; paths must not overlap x or the states (NULL is allowed when n = 0).  status: DEVICE int [L] or NULL:
+ *   0 ok; 1 Kalman DARE not converged (that latent's rows and states_out NaN for every sample).  Returns 1 (and launches nothing) for bad
+ *   arguments; 3 for stacked models.  Asynchronous on `stream`, with the handle's stream bookkeeping as for a forecast; the smoother's tables are
+ *   built on the first call that needs them after a table rewrite.
+ *   Chaining: a call for n1 steps followed by a call with its states_out as states_in, step0 = n1 and n2 steps reproduces one call of n1 + n2
+ *   steps bit for bit, for any n1 (hence the fp64 states and step0): S x L x n can be generated in slabs.  Ranges of samples (sample0) and banks
+ *   that hold ranges of latents (latent0) reproduce the rows of one large call likewise.
+ * moihgp_forecast_paths_noise: the normals above without a handle -- noise [S][L][ld] (DEVICE float), n[step0 + j] of latent latent0 + l and
+ *   sample sample0 + s at [s][l][j], j < n <= ld.  Asynchronous on `stream`.  The way to audit a path. */
+int moihgp_forecast_paths(moihgp_gp* gp, int dtype, const void* x, const double* states_in, double* states_out,
+                          size_t n, size_t step0, size_t nsamples, unsigned long long seed, unsigned sample0, unsigned latent0,
+                          void* paths, size_t ld_out, size_t plane_stride, int* status, void* stream);
+int moihgp_forecast_paths_noise(unsigned long long seed, unsigned latent0, size_t L, unsigned sample0, size_t S,
+                                size_t step0, size_t n, float* noise, size_t ld, void* stream);
+
 /* As above plus the hyper-parameter sensitivities (ihgp.h:54) and the per-latent NLL gradient
  * (ihgp.h:216-220), summed over ticks:
  *   dx   [L][P][d] in/out (dtype);  grad [L][P] doubles out. */

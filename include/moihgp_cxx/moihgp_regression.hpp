@@ -161,6 +161,29 @@ public:
             return rc ? rc : d.fetch(d.buf[1]);
         }, [](size_t l, int) { return "the Kalman DARE of latent " + std::to_string(l) + " did not converge"; })[0];
     }
+    // (not in the reference) Seeded joint draws of the n ticks beyond the series with the current parameters (include/moihgp.h
+    // moihgp_forecast_paths): element [s][j] is draw s of every output's observation at tick T + j given ALL of Y -- whole trajectories whose
+    // covariance across horizons is the GP predictive one, inside the mixing's span and with the latents' noise -- from a zero start state.  The
+    // same seed gives the same paths; they are not jointly consistent with sampleSmoothed() of the same series.  fp64 on the device:
+    // project_stream -> the end state with the Kalman gains (forecast_scores, which writes no plane) -> forecast_paths -> unproject_stream per
+    // sample.  Throws std::invalid_argument for an empty series, n outside 0 .. 2^20 or nsamples outside 1 .. 65535, and std::runtime_error if a
+    // latent's Kalman DARE did not converge (status 1: its rows would be NaN).  Missing outputs (NaN) are projected as in predictSmoothed().
+    std::vector<std::vector<Vector>> samplePathsAhead(const std::vector<Vector>& Y, size_t n, size_t nsamples, unsigned long long seed = 0) {
+        if (nsamples < 1 || nsamples > 65535) throw std::invalid_argument("samplePathsAhead: nsamples must be 1 .. 65535");
+        if (n > ((size_t)1 << 20)) throw std::invalid_argument("samplePathsAhead: n must be 0 .. 2^20");
+        if (Y.empty()) throw std::invalid_argument("samplePathsAhead: the series is empty");
+        const size_t T = Y.size(), L = _num_latent, M = _num_output, ld = (T + 1) / 2 * 2, ldn = (n + 1) / 2 * 2, S = nsamples;
+        if (n == 0) return std::vector<std::vector<Vector>>(S);
+        const int one = 1;
+        return streamRoundTrip("samplePathsAhead", Y, {L * ld, 2 * L, S * L * ldn, n * M}, [&](StreamTrip& d) {
+            int rc = d.project();
+            if (!rc) rc = moihgp_forecast_scores(d.h, MOIHGP_F64, d.buf[0], T, ld, d.x, d.x, &one, 1, 0, MOIHGP_GAINS_KALMAN,
+                                                 reinterpret_cast<long long*>(d.buf[1]), nullptr, d.buf[1] + L, nullptr, d.status, d.s);
+            if (!rc) rc = moihgp_forecast_paths(d.h, MOIHGP_F64, d.x, nullptr, nullptr, n, 0, S, seed, 0, 0, d.buf[2], ldn, L * ldn, d.status, d.s);
+            for (size_t k = 0; k < S && !rc; k++) rc = d.fetchAhead(d.buf[2] + k * L * ldn, n, ldn, d.buf[3]);
+            return rc;
+        }, [](size_t l, int) { return "the Kalman DARE of latent " + std::to_string(l) + " did not converge"; });
+    }
     // (not in the reference) Fixed-lag smoothing of the series with the current parameters (include/moihgp.h moihgp_lagged_stream): element t is the
     // mean of every output at tick t given Y[0 .. min(t + lag, T - 1)], from a zero start state -- predictAhead(Y, 0) at lag 0, predictSmoothed(Y)
     // once lag >= T.  fp64 on the device: project_stream -> lagged_stream -> unproject_stream.  Throws std::invalid_argument for a lag outside
@@ -253,15 +276,21 @@ private:
         Vector flat;
         std::vector<std::vector<Vector>> planes;
         int project() { return moihgp_project_stream(h, MOIHGP_F64, Y, T, buf[0], ld, s); }          // Y -> buf[0], series-major rows of ld
-        int take() {                                                                                  // Y -> the next plane of the result
-            if (int rc = moihgp_dvec_download(ctx, flat.data(), Y, T * M)) return rc;
-            planes.push_back(std::vector<Vector>(T, Vector(M)));
-            for (size_t t = 0; t < T; t++) for (size_t m = 0; m < M; m++) planes.back()[t][m] = flat[t * M + m];
+        int take() { return takeFrom(Y, T); }                                                        // Y -> the next plane of the result
+        int takeFrom(const double* src, size_t n) {                                                   // n ticks [n][M] at src -> the next plane
+            if (flat.size() < n * M) flat.resize(n * M);
+            if (int rc = moihgp_dvec_download(ctx, flat.data(), src, n * M)) return rc;
+            planes.push_back(std::vector<Vector>(n, Vector(M)));
+            for (size_t t = 0; t < n; t++) for (size_t m = 0; m < M; m++) planes.back()[t][m] = flat[t * M + m];
             return 0;
         }
         int fetch(const double* rows) {                                                               // un-project series-major rows, then take()
             const int rc = moihgp_unproject_stream(h, MOIHGP_F64, rows, T, ld, Y, s);
             return rc ? rc : take();
+        }
+        int fetchAhead(const double* rows, size_t n, size_t ldn, double* Yn) {                        // ... n ticks past the series, through Yn [n][M]
+            const int rc = moihgp_unproject_stream(h, MOIHGP_F64, rows, n, ldn, Yn, s);
+            return rc ? rc : takeFrom(Yn, n);
         }
     };
     // The round trip itself, fp64 from a zero start state: flatten Y, create the context and the device vectors (Y, x, the status words, and one per

@@ -29,6 +29,7 @@ ADDITIVE_SYMBOLS = [
     "moihgp_interp_stream", "moihgp_interp_variances",
     "moihgp_slope_stream", "moihgp_slope_variances",
     "moihgp_sample_stream", "moihgp_sample_noise", "moihgp_get_sampler",
+    "moihgp_forecast_paths", "moihgp_forecast_paths_noise",
     "moihgp_dvec_ctx_new", "moihgp_dvec_ctx_del", "moihgp_dvec_ctx_stream", "moihgp_dvec_alloc", "moihgp_dvec_alloc_mask", "moihgp_dvec_free", "moihgp_dvec_trim", "moihgp_dvec_cache_limit", "moihgp_dvec_upload", "moihgp_dvec_download",
     "moihgp_dvec_copy", "moihgp_dvec_sync", "moihgp_dvec_dot", "moihgp_dvec_axpy", "moihgp_dvec_scale", "moihgp_dvec_sub", "moihgp_dvec_clamp", "moihgp_dvec_active_set",
     "moihgp_dvec_proj_step", "moihgp_dvec_proj_grad_norm",
@@ -169,6 +170,12 @@ def load_library():
                                         C.c_void_p]
     lib.moihgp_get_sampler.restype = C.c_int
     lib.moihgp_get_sampler.argtypes = [C.c_void_p, C.c_size_t] + [c_double_p] * 5 + [C.POINTER(C.c_int)]
+    lib.moihgp_forecast_paths.restype = C.c_int
+    lib.moihgp_forecast_paths.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint64,
+                                          C.c_uint, C.c_uint, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
+    lib.moihgp_forecast_paths_noise.restype = C.c_int
+    lib.moihgp_forecast_paths_noise.argtypes = [C.c_uint64, C.c_uint, C.c_size_t, C.c_uint, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                C.c_void_p]
     lib.moihgp_forecast_variances.restype = C.c_int
     lib.moihgp_forecast_variances.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_size_t, c_double_p]
     lib.moihgp_forecast_scores.restype = C.c_int

@@ -1493,6 +1493,55 @@ int moihgp_get_sampler(moihgp_gp* gp, size_t l, double* B, double* sigma2, doubl
     return guard_rc([&] { return get_sampler_impl(gp, l, B, sigma2, Sigma, Lc, acov_err, status); });
 }
 
+// ---- seeded forecast paths (paths.hip) ------------------------------------------------------------------------------------------------------------
+// Draws of the ticks beyond a stream from its end state x, or continued from the fp64 states of an earlier call; the smoother's tables give K and P.
+static int forecast_paths_impl(moihgp_gp* gp, int dtype, const void* x, const double* states_in, double* states_out, size_t n, size_t step0,
+                               size_t nsamples, unsigned long long seed, unsigned sample0, unsigned latent0, void* paths, size_t ld_out,
+                               size_t plane_stride, int* status, void* stream) {
+    if (int rc = check_handle_dtype(gp, dtype)) return rc;
+    if (!x == !states_in) { set_last_error("forecast_paths: exactly one of x and states_in must be given"); return 1; }
+    if (nsamples < 1 || nsamples > 65535) { set_last_error("forecast_paths: nsamples (%zu) must be 1 .. 65535", nsamples); return 1; }
+    if (n > ((size_t)1 << 20)) { set_last_error("forecast_paths: n (%zu) must be <= 2^20", n); return 1; }
+    if (step0 > ((size_t)1 << 32) - n) { set_last_error("forecast_paths: step0 + n (%zu + %zu) must be <= 2^32", step0, n); return 1; }
+    const SweepIo io = stream_sweep_io(gp, dtype, nullptr, n, 0, x, nullptr, nullptr, ld_out, stream);      // (no input stream: T = n for the rows)
+    if (int rc = check_outputs(io, {{paths, "path buffer", "the path buffer", nsamples, plane_stride}})) return rc;
+    if (kernel_stack(gp->kernel)) { set_last_error("forecast: stacked models are not supported (Matern-3/2 and -5/2 only)"); return 3; }
+    // every lane reads its start before the wavefront's first store and its neighbours' rows are written by its own wavefront: the start state
+    // and the fp64 states may not lie inside the planes
+    const size_t es = dtype == MOIHGP_F64 ? 8 : 4, plane_elems = (nsamples - 1) * plane_stride + gp->L * ld_out;
+    const size_t state_elems = nsamples * gp->L * (size_t)gp->d * (8 / es);                                 // (in scalars of the planes' type)
+    if (int rc = check_no_overlap(x, gp->L * (size_t)gp->d, paths, plane_elems, n, es, "the path buffer must not overlap x")) return rc;
+    if (int rc = check_no_overlap(states_in, state_elems, paths, plane_elems, n, es, "the path buffer must not overlap states_in")) return rc;
+    if (int rc = check_no_overlap(states_out, state_elems, paths, plane_elems, n, es, "the path buffer must not overlap states_out")) return rc;
+    if ((gp->L * nsamples + 63) / 64 > 0x7fffffffu) { set_last_error("forecast_paths: too many rows (L * nsamples = %zu)", gp->L * nsamples); return 1; }
+    if (int rc = ensure_smoother(gp, io.stream)) return rc;
+    note_user_stream(gp, io.stream);
+    launch_forecast_paths(gp->d, dtype, gp->sm.d, gp->cb64, gp->L, x, states_in, states_out, n, step0, seed, sample0, latent0,
+                          SweepPlanes{paths, plane_stride, (int)nsamples}, ld_out, status, io.stream);
+    return 0;
+}
+
+static int forecast_paths_noise_impl(unsigned long long seed, unsigned latent0, size_t L, unsigned sample0, size_t S, size_t step0, size_t n, float* noise,
+                                     size_t ld, void* stream) {
+    if (n > 0 && L > 0 && S > 0 && !noise) { set_last_error("forecast_paths_noise: null noise buffer"); return 1; }
+    if (ld < n) { set_last_error("forecast_paths_noise: ld (%zu) must be >= n", ld); return 1; }
+    if (n > ((size_t)1 << 32) || step0 > ((size_t)1 << 32) - n) { set_last_error("forecast_paths_noise: step0 + n (%zu + %zu) must be <= 2^32", step0, n); return 1; }
+    launch_forecast_paths_noise(seed, latent0, L, sample0, S, step0, n, noise, ld, (hipStream_t)stream);
+    return 0;
+}
+
+int moihgp_forecast_paths(moihgp_gp* gp, int dtype, const void* x, const double* states_in, double* states_out, size_t n, size_t step0, size_t nsamples,
+                          unsigned long long seed, unsigned sample0, unsigned latent0, void* paths, size_t ld_out, size_t plane_stride, int* status,
+                          void* stream) {
+    return guard_rc([&] {
+        return forecast_paths_impl(gp, dtype, x, states_in, states_out, n, step0, nsamples, seed, sample0, latent0, paths, ld_out, plane_stride, status, stream);
+    });
+}
+int moihgp_forecast_paths_noise(unsigned long long seed, unsigned latent0, size_t L, unsigned sample0, size_t S, size_t step0, size_t n, float* noise,
+                                size_t ld, void* stream) {
+    return guard_rc([&] { return forecast_paths_noise_impl(seed, latent0, L, sample0, S, step0, n, noise, ld, stream); });
+}
+
 int moihgp_stream_retile(int dtype, const void* src, void* dst, size_t L, size_t T, size_t ld, int to_tiled, void* stream) {
     return guard_rc([&] {
         if (int rc = check_dtype(dtype)) return rc;

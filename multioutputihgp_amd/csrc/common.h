@@ -297,6 +297,13 @@ void launch_sample_stream(int d, const SweepIo& io, const double* sm, const doub
                           unsigned sample0, unsigned latent0, int* status, int path);
 void launch_sample_noise(unsigned long long seed, unsigned latent0, size_t L, unsigned sample0, size_t S, size_t T, float* noise, size_t ld, float* start,
                          hipStream_t stream);
+// paths.hip: seeded forecast paths beyond the end of a stream (moihgp_forecast_paths).  x [L][d] (dtype) or states_in [S][L][d] (fp64): exactly one
+// of them; paths.K = S planes of L rows, ld_out apart; sm: the smoother's blocks, cb64: the constant blocks (the noise parameter)
+void launch_forecast_paths(int d, int dtype, const double* sm, const double* cb64, size_t L, const void* x, const double* states_in, double* states_out,
+                           size_t n, size_t step0, unsigned long long seed, unsigned sample0, unsigned latent0, const SweepPlanes& paths, size_t ld_out,
+                           int* status, hipStream_t stream);
+void launch_forecast_paths_noise(unsigned long long seed, unsigned latent0, size_t L, unsigned sample0, size_t S, size_t step0, size_t n, float* noise,
+                                 size_t ld, hipStream_t stream);
 // series-major [L][ld] <-> segment-major [ceil(T / SEG)][L][SEG] (to_tiled != 0: src is series-major; ticks past T are written as zeros)
 int launch_stream_retile(int dtype, const void* src, void* dst, size_t L, size_t T, size_t ld, int to_tiled, hipStream_t stream);
 // recursion.hip: batched sweeps over series-major streams.

@@ -153,19 +153,26 @@ def _first_origin(t_first, T: int) -> int:
     return int(t_first)
 
 
-def _plane_out_strides(out: torch.Tensor, K: int, L: int, T: int, Ty: torch.Tensor):
-    """(ld_out, plane_stride) of a buffer of K planes [K, L, >=T] (forecast horizons, posterior samples) for the stream Ty, or ValueError:
-    dtype, device, shape, unit stride along time, row and plane strides multiples of 16 bytes, rows >= T rounded up, planes >= L rows, and no overlap with Ty."""
-    epv = 2 if Ty.dtype == torch.float64 else 4
-    ok = (out.device == Ty.device and out.dtype == Ty.dtype and out.dim() == 3 and out.shape[0] == K and out.shape[1] == L and out.shape[2] >= T
+def _plane_strides(out: torch.Tensor, K: int, L: int, T: int, dtype, device):
+    """(ld_out, plane_stride) of a buffer of K planes [K, L, >=T] of `dtype` on `device`, or ValueError: shape, unit stride along time, row and plane
+    strides multiples of 16 bytes, rows >= T rounded up, planes >= L rows."""
+    epv = 2 if dtype == torch.float64 else 4
+    ok = (out.device == device and out.dtype == dtype and out.dim() == 3 and out.shape[0] == K and out.shape[1] == L and out.shape[2] >= T
           and (out.shape[2] <= 1 or out.stride(2) == 1) and out.data_ptr() % 16 == 0)
     if ok:
-        ld_out = out.stride(1) if L > 1 else padded_len(max(T, 1), Ty.dtype)
+        ld_out = out.stride(1) if L > 1 else padded_len(max(T, 1), dtype)
         plane = out.stride(0) if K > 1 else L * ld_out
-        ok = ld_out % epv == 0 and ld_out >= padded_len(T, Ty.dtype) and plane % epv == 0 and plane >= L * ld_out
+        ok = ld_out % epv == 0 and ld_out >= padded_len(T, dtype) and plane % epv == 0 and plane >= L * ld_out
     if not ok:
         raise ValueError("out must be a tensor [K, L, >=T] of the stream's dtype and device, 16-byte aligned, unit stride along time, row stride a "
                          "multiple of 16 bytes and >= T rounded up to it, plane stride a multiple of 16 bytes and >= L rows")
+    return ld_out, plane
+
+
+def _plane_out_strides(out: torch.Tensor, K: int, L: int, T: int, Ty: torch.Tensor):
+    """(ld_out, plane_stride) of a buffer of K planes [K, L, >=T] (forecast horizons, posterior samples) for the stream Ty, or ValueError:
+    dtype, device, shape, unit stride along time, row and plane strides multiples of 16 bytes, rows >= T rounded up, planes >= L rows, and no overlap with Ty."""
+    ld_out, plane = _plane_strides(out, K, L, T, Ty.dtype, Ty.device)
     es = Ty.element_size()
     a0, a1 = Ty.data_ptr(), Ty.data_ptr() + L * Ty.stride(0) * es
     b0, b1 = out.data_ptr(), out.data_ptr() + ((K - 1) * plane + L * ld_out) * es
@@ -646,6 +653,81 @@ class LatentBank:
         _check(self._lib.moihgp_forecast_variances(self._h, hz, K, var.ctypes.data_as(c_double_p)), self._lib)
         return var
 
+    def forecast_paths(self, x: Optional[torch.Tensor] = None, n: Optional[int] = None, nsamples: Optional[int] = None, seed: int = 0, sample0: int = 0,
+                       latent0: int = 0, step0: int = 0, states: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                       want_states: bool = True, stream=None):
+        """Seeded joint draws of the n ticks beyond a stream for every latent (include/moihgp.h moihgp_forecast_paths): paths[s, l, j] is a draw of
+        the OBSERVATION of latent l at tick T + step0 + j (noise included) given the ticks up to the end state and nothing else, with the GP
+        predictive covariance across horizons (path_covariance()); the mean over draws is forecast_tail().  The draws are not jointly consistent with
+        a sample() draw of the same stream.  Start: `x` [L, d], a stream's end state with the Kalman gains (forecast(), forecast_scores(), smooth()),
+        shared by all samples -- or `states` [S, L, d] float64, the states an earlier call returned, with `step0` the number of steps already
+        drawn: the calls then reproduce one long call bit for bit.  The noise is Philox4x32-10 keyed by `seed` and counted by
+        (step0 + j, latent0 + l, sample0 + s), so ranges of samples or latents reproduce one large call too.
+
+        Returns (paths [S, L, >=n], states [S, L, d] float64 or None, status [L] int32: 0 ok, 1 Kalman DARE not converged (rows and states NaN)).
+        The dtype is x's, or `out`'s when `states` is given (float64 without `out`).  Asynchronous on the current torch stream.  `out` (optional)
+        [S, L, >=n] as forecast()'s; it must not overlap x or the states."""
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= n <= (1 << 20):
+            raise ValueError(f"n {n!r} must be an integer in 0 .. 2^20")
+        if isinstance(nsamples, bool) or not isinstance(nsamples, (int, np.integer)) or not 1 <= nsamples <= 65535:
+            raise ValueError(f"nsamples {nsamples!r} must be an integer in 1 .. 65535")
+        if isinstance(step0, bool) or not isinstance(step0, (int, np.integer)) or not 0 <= step0 <= (1 << 32) - n:
+            raise ValueError(f"step0 {step0!r} must be an integer with 0 <= step0 and step0 + n <= 2^32")
+        n, S, step0 = int(n), int(nsamples), int(step0)
+        seed, sample0, latent0 = int(seed), int(sample0), int(latent0)
+        if not (0 <= seed < 1 << 64 and 0 <= sample0 < 1 << 32 and 0 <= latent0 < 1 << 32):
+            raise ValueError("seed must be in 0 .. 2^64 - 1, sample0 and latent0 in 0 .. 2^32 - 1")
+        if (x is None) == (states is None):
+            raise ValueError("exactly one of x and states must be given")
+        if x is not None:
+            if not x.is_cuda or x.dtype not in _DT or not x.is_contiguous() or tuple(x.shape) != (self.L, self.d):
+                raise ValueError("x must be a contiguous CUDA tensor [L, d] (float32/float64)")
+            dtype, device, start = x.dtype, x.device, x
+        else:
+            if not states.is_cuda or states.dtype != torch.float64 or not states.is_contiguous() or tuple(states.shape) != (S, self.L, self.d):
+                raise ValueError("states must be a contiguous float64 CUDA tensor [S, L, d]")
+            dtype, device, start = (torch.float64 if out is None else out.dtype), states.device, states
+            if dtype not in _DT:
+                raise ValueError("out must be float32 or float64")
+        self._refuse_stacked("forecast_paths")
+        if out is None:
+            out = torch.empty((S, self.L, padded_len(max(n, 1), dtype)), dtype=dtype, device=device)[:, :, :n]
+        ld_out, plane = _plane_strides(out, S, self.L, n, dtype, device)
+        states_out = torch.empty((S, self.L, self.d), dtype=torch.float64, device=device) if want_states else None
+        b0, b1 = out.data_ptr(), out.data_ptr() + ((S - 1) * plane + self.L * ld_out) * out.element_size()
+        for t in (start, states_out):
+            if t is not None and n > 0 and t.data_ptr() < b1 and b0 < t.data_ptr() + t.numel() * t.element_size():
+                raise ValueError("out must not overlap x or the states")
+        status = torch.empty((self.L,), dtype=torch.int32, device=device)
+        rc = self._lib.moihgp_forecast_paths(self._h, _DT[dtype], C.c_void_p(x.data_ptr()) if x is not None else None,
+                                             C.c_void_p(states.data_ptr()) if states is not None else None,
+                                             C.c_void_p(states_out.data_ptr()) if want_states else None, n, step0, S, seed, sample0, latent0,
+                                             C.c_void_p(out.data_ptr()), ld_out, plane, C.c_void_p(status.data_ptr()), _stream_ptr(stream))
+        _check(rc, self._lib)
+        return out, states_out, status
+
+    def path_covariance(self, l: int, n: int):
+        """(C [n, n], taps [n]) of latent l, fp64 numpy, on the host: the covariance across horizons of forecast_paths()' draws, C = Sv Lam Lam^T
+        with Lam lower-triangular Toeplitz of the taps lam_0 = 1, lam_k = (A^k K)_0 and Sv = P_00 + R = P_00 / K_0 (latent(l)["A"] and
+        smoother(l)).  Its diagonal is forecast_variances([j + 1]) + R; 1^T C 1 is the variance of the sum over the next n ticks.  NaN for a
+        latent whose Kalman DARE did not converge."""
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= n <= (1 << 20):
+            raise ValueError(f"n {n!r} must be an integer in 0 .. 2^20")
+        n = int(n)
+        self._refuse_stacked("path_covariance")
+        A, sm = self.latent(int(l))["A"], self.smoother(int(l))
+        if np.isnan(self.forecast_variances([1])[0, int(l)]):
+            return np.full((n, n), np.nan), np.full(n, np.nan)
+        K, Sv = sm["K"], sm["P"][0, 0] / sm["K"][0]
+        taps, v = np.ones(n), K.copy()
+        for k in range(1, n):
+            v = A @ v
+            taps[k] = v[0]
+        Lam = np.zeros((n, n))
+        for k in range(n):
+            Lam[np.arange(k, n), np.arange(0, n - k)] = taps[k]
+        return Sv * (Lam @ Lam.T), taps
+
 
 def project_stream(gp, Y: torch.Tensor, stream=None) -> torch.Tensor:
     """OILMM projection of a tick-major observation stream Y [T, M] with the mixing of `gp`
@@ -832,6 +914,39 @@ def forecast_outputs(gp, Y: torch.Tensor, horizons, tail: int = 0, gains: str = 
     # (with gains "handle" the means exist, but var_Y does not)
     return Yf, _output_variances(gp, var, bad, f"forecast_outputs: the Kalman DARE of {bad} latent(s) did not converge; their rows and variances are NaN "
                                  "and so is every output that mixes them"), Ytail
+
+
+def forecast_paths_noise(seed: int, L: int, S: int, n: int, step0: int = 0, latent0: int = 0, sample0: int = 0, device="cuda", stream=None) -> torch.Tensor:
+    """The normals of LatentBank.forecast_paths without a handle (moihgp_forecast_paths_noise): noise [S, L, n] float32 with noise[s, l, j] the normal
+    of step step0 + j, latent latent0 + l, sample sample0 + s.  The way to audit a path."""
+    lib = load_library()
+    ld = padded_len(max(n, 1), torch.float32)
+    noise = torch.empty((S, L, ld), dtype=torch.float32, device=device)
+    _check(lib.moihgp_forecast_paths_noise(int(seed), int(latent0), L, int(sample0), S, int(step0), int(n), C.c_void_p(noise.data_ptr()), ld,
+                                           _stream_ptr(stream)), lib)
+    return noise[:, :, :n]
+
+
+def forecast_path_outputs(gp, Y: torch.Tensor, n: int, nsamples: int, seed: int = 0, stream=None):
+    """Joint draws of the outputs at the n ticks beyond a tick-major observation stream Y [T, M] (NaN = missing output) with the parameters of `gp`
+    (a pywrapper.MOIHGP), from a zero state: project_stream -> the end state with the Kalman gains (forecast_scores, which writes no plane) ->
+    LatentBank.forecast_paths -> unproject_stream per sample, and forecast_tail for the mean.
+
+    Returns (Ypaths [S, n, M] in Y's dtype, Ymean [n, M]).  Ypaths[s, j] is a draw of the outputs' observation process at tick T + j inside the
+    mixing's span, with the latents' noise (the sigma^2 component outside the span is not drawn); Ymean[j] the mean at tick T + j given all T
+    ticks.  Raises MoihgpError if any latent's Kalman DARE did not converge.  Missing outputs as forecast_outputs."""
+    _check_observations(gp, Y)
+    bank = LatentBank.from_handle(gp)
+    Ty = project_stream(gp, Y, stream=stream)
+    x = bank.forecast_scores(Ty, [1], T=Y.shape[0], stream=stream)["x"]
+    paths, _, status = bank.forecast_paths(x, n, nsamples, seed=seed, want_states=False, stream=stream)
+    Ypaths = torch.stack([unproject_stream(gp, paths[s], n, stream=stream) for s in range(paths.shape[0])])
+    Ymean = unproject_stream(gp, bank.forecast_tail(x, n, stream=stream), n, stream=stream)
+    bad = int((status != 0).sum())      # (synchronises)
+    if bad:
+        raise MoihgpError(f"forecast_path_outputs: the Kalman DARE of {bad} latent(s) did not converge; their rows are NaN and so is every output "
+                          "that mixes them", 1)
+    return Ypaths, Ymean
 
 
 def score_summary(scores: dict) -> dict:
