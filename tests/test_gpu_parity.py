@@ -427,7 +427,8 @@ def test_time_split_matches_unsplit(env, dtype, L, T, nan, monkeypatch):
 
 # ------------------------------------------------------------------------------------------ A8: polar factor on the device
 @pytest.mark.parametrize("M,L,noise", [(8, 4, 0.3), (100, 70, 0.2), (300, 300, 0.05), (1024, 512, 0.02), (64, 64, 2.0),
-                                       (64, 16, 0.5), (128, 32, 0.2), (1000, 4, 1.0), (40, 20, 2.0), (5, 5, 0.4), (3, 1, 0.0)])
+                                       (64, 16, 0.5), (128, 32, 0.2), (1000, 4, 1.0), (40, 20, 2.0), (5, 5, 0.4), (3, 1, 0.0),
+                                       (140, 129, 0.2), (300, 257, 0.05)])     # the last two: odd L over more than one tile (scalar fetches, the mirror)
 def test_polar_factor_device_vs_svd(env, M, L, noise, monkeypatch):
     """MOIHGP::update (moihgp.h:433-447) forms U = svdU svdV^T.  On the device it is Newton-Schulz: one workgroup in LDS for
     small matrices (M L <= 4096, L <= 32), MFMA GEMMs otherwise (MOIHGP_POLAR=gemm forces those)."""
@@ -551,7 +552,8 @@ def test_gradstream_segment_boundaries_of_the_long_stream_kernels(env, dtype, ke
 
 # ------------------------------------------------------------------------------------------ windowed objective in one call
 @pytest.mark.parametrize("kern,M,L,W", [("Matern32", 6, 3, 5), ("Matern52", 8, 8, 16), ("Matern52", 70, 33, 128), ("Matern32", 300, 200, 40),
-                                        ("Matern52", 6, 4, 1100)])     # the last one: predicted means out of full 512-tick segments
+                                        ("Matern52", 6, 4, 1100),      # predicted means out of full 512-tick segments
+                                        ("Matern32", 130, 129, 70)])   # a 2 x 2 tile U-gradient with two full k tiles and a tail
 def test_window_objective_vs_oracle_loop(env, kern, M, L, W):
     """moihgp_window_set/eval == the learners' loop (moihgp_online.h:61-70): step with sensitivities, NLL + gradient on the
     pre-step state, summed over the window; checked against the oracle's per-tick calls and against our own per-tick ABI."""
