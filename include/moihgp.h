@@ -269,6 +269,39 @@ int moihgp_get_smoother(moihgp_gp* gp, size_t l, double* P, double* K, double* G
                         double* var_filtered, double* var_smoothed);
 int moihgp_latent_variances(moihgp_gp* gp, double* var_filtered, double* var_smoothed);
 
+/* ---- exact-edge smoothing of whole streams, with per-tick variances (not in the reference) ------------------------------------------------
+ * The steady sweeps of moihgp_smooth_stream are the exact smoother of the model under the prior x_0 ~ N(A x_in, P) on the first state; the model's
+ * own prior is N(0, Pinf).  Swapping a Gaussian prior on a d-dimensional state is a rank-d update of the whole smoothed trajectory, and the
+ * steady smoothed variance is wrong at both ends of a stream (the backward recursion starts from PF, not Ps).  Per latent, take the smoother's
+ * tables A, K, G, P, PF, Ps and the model's Pinf, and run moihgp_smooth_stream's two passes from a ZERO start state: p[t], v[t], xf[t], s[t],
+ * ys[t] = p[t] + s[t]_0.  Then:
+ *     Ps_t :  Ps_{T-1} = PF,   Ps_t = PF + G (Ps_{t+1} - P) G^T            (backward; reaches the tables' Ps away from the end)
+ *     E  = Pinf^-1 - P^-1,     Z = -(I + E Ps_0)^-1 E                       (d x d, symmetric; no inverse of Ps)
+ *     r_t = e0^T Ps_t (G^T)^t                                               (row vector, decays like G^t)
+ *     ysmooth[t] = ys[t] + r_t Z s[0]
+ *     var[t]     = (Ps_t)_00 + r_t Z r_t^T                                  (variance of the latent FUNCTION, no noise)
+ *     x          = xf[T-1] + PF (G^T)^(T-1) Z s[0]
+ * s[0] is the full d-vector the backward pass holds when it leaves tick 0 (with a zero start, the smoothed state at tick 0).  For a gap-free
+ * stream these formulas are the GP posterior at every tick, for any T >= 1.  With missing ticks the steady sweeps are themselves approximate
+ * near the gaps, as in moihgp_smooth_stream; the correction is applied unchanged and no exactness is claimed there.  Start states are not taken:
+ * the start is the prior.
+ * Edge lengths, per latent, from the tables: head is the smallest n with |G^n|inf <= 2^-60, tail the smallest k with |G^k|inf^2 <= 2^-60; both are
+ * capped at 2^20, and the cap means "never reached".  Ticks in [head, T - tail) are not touched: there ysmooth holds the bits moihgp_smooth_stream
+ * writes (from a zero start state) and var the stream-dtype rounding of var_smoothed; x is corrected only when T <= head.  When the two edges of
+ * a latent overlap (head + tail > T) the head needs the tail's Ps_t, which goes through a scratch buffer of 8 d T L bytes on the handle, for
+ * streams of at most 4096 ticks.
+ * moihgp_smooth_stream_exact: Ty, ld_in, ysmooth, ld_out, alignment, overlap rules, asynchrony and stream bookkeeping as moihgp_smooth_stream.
+ *   x [L][d] receives the end state (output only).  var [L][ld_out] (dtype) or NULL: a second row-shaped output that may overlap neither Ty nor
+ *   ysmooth; NULL writes no variance.  status: DEVICE int [L] or NULL: 0 ok; 1 Kalman DARE not converged (rows and end state NaN, as
+ *   moihgp_smooth_stream); 3 the edges overlap in a stream longer than 4096 ticks (ysmooth and x are moihgp_smooth_stream's, var is
+ *   var_smoothed at every tick); 4 the edge tables failed (Pinf or P could not be inverted, or something is not finite; the rows as for 3).
+ *   Honours the option "smoother_path".  The edge tables are built with the smoother's, on the first call after a table rewrite; that call also
+ *   reads the largest head + tail back once and so synchronises.  Stacked models: 3.
+ * moihgp_edge_lengths: head [L], tail [L] to HOST buffers (either may be NULL).  Synchronises. */
+int moihgp_smooth_stream_exact(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, void* x, void* ysmooth, void* var, size_t ld_out,
+                               int* status, void* stream);
+int moihgp_edge_lengths(moihgp_gp* gp, int* head, int* tail);
+
 /* ---- multi-horizon forecasts of whole streams, with variances (not in the reference, whose only route is the per-tick ABI: one step(x, y) and
  * then h prediction-only step(x) calls per tick and per horizon, ihgp.h:96-100) --------------------------------------------------------------
  * Per latent, A the handle's A, H = e0, and gains (K, M):

@@ -126,6 +126,45 @@ public:
             return rc ? rc : d.fetch(d.buf[1]);
         }, [](size_t l, int) { return "the Kalman DARE of latent " + std::to_string(l) + " did not converge"; })[0];
     }
+    // (not in the reference) predictSmoothed() with exact edges (include/moihgp.h moihgp_smooth_stream_exact): the posterior mean of every output
+    // at every tick given ALL of Y under the model's own prior on the first state -- for a series without missing outputs the GP posterior at
+    // every tick, where predictSmoothed() is approximate near the start.  varY (if not null) receives, per entry of `ticks` (negative: counted
+    // from the end), the posterior variance of the latent FUNCTION behind every output at that tick, without the observation noise:
+    // (*varY)[k][m] = sum_l U[m][l]^2 S_l var[l][ticks[k]].  fp64 on the device: project_stream -> smooth_stream_exact -> unproject_stream.
+    // Throws std::invalid_argument for a tick outside -T .. T - 1 and std::runtime_error on a non-zero status (1 Kalman DARE not converged, 3 a
+    // latent's edges overlap in a series longer than 4096 ticks, 4 its edge tables failed).  Missing outputs (NaN) are projected as in
+    // predictSmoothed(); no exactness is claimed near them.
+    std::vector<Vector> predictSmoothedExact(const std::vector<Vector>& Y, const std::vector<long>& ticks = std::vector<long>(),
+                                             std::vector<Vector>* varY = nullptr) {
+        const size_t T = Y.size(), L = _num_latent, M = _num_output, ld = (T + 1) / 2 * 2;
+        for (long t : ticks)
+            if (t < -(long)T || t >= (long)T) throw std::invalid_argument("predictSmoothedExact: ticks must lie in -T .. T - 1");
+        if (varY) varY->assign(ticks.size(), Vector(M, 0.0));
+        if (T == 0) return std::vector<Vector>();
+        Vector var(varY ? L * ld : 0);
+        std::vector<Vector> Ys = streamRoundTrip("predictSmoothedExact", Y, {L * ld, L * ld, L * ld}, [&](StreamTrip& d) {
+            int rc = d.project();
+            if (!rc) rc = moihgp_smooth_stream_exact(d.h, MOIHGP_F64, d.buf[0], T, ld, d.x, d.buf[1], varY ? d.buf[2] : nullptr, ld, d.status, d.s);
+            if (!rc && varY) rc = moihgp_dvec_download(d.ctx, var.data(), d.buf[2], L * ld);
+            return rc ? rc : d.fetch(d.buf[1]);
+        }, [](size_t l, int status) {
+            return "latent " + std::to_string(l) + " has status " + std::to_string(status) +
+                   (status == 1 ? " (the Kalman DARE did not converge)"
+                    : status == 3 ? " (its edges overlap in a series longer than 4096 ticks)" : " (its edge tables failed)");
+        })[0];
+        if (varY) {
+            const Vector prm = _moihgp->getParams();                 // [U row-major | S | ...]
+            for (size_t k = 0; k < ticks.size(); k++) {
+                const size_t t = (size_t)(ticks[k] < 0 ? ticks[k] + (long)T : ticks[k]);
+                for (size_t m = 0; m < M; m++) {
+                    double a = 0.0;
+                    for (size_t l = 0; l < L; l++) a += prm[m * L + l] * prm[m * L + l] * (prm[M * L + l] * var[l * ld + t]);
+                    (*varY)[k][m] = a;
+                }
+            }
+        }
+        return Ys;
+    }
     // (not in the reference) Seeded joint posterior samples of the whole series with the current parameters (include/moihgp.h
     // moihgp_sample_stream): element [s][t] is sample s of every output at tick t given ALL of Y -- the smoothed mean of predictSmoothed() plus a
     // draw of the steady-state deviation process (exact covariance in the interior of a long gap-free series, under-dispersed near its ends and

@@ -147,6 +147,16 @@ struct moihgp_gp {
     // steady-state RTS smoother (moihgp_smooth_stream): its per-latent tables, built lazily on the first smooth after a table rewrite
     LazyTables sm;
     int opt_smoother_path = -1;          // option "smoother_path": -1 automatic, 0 scan kernels, 1 serial fp64
+    // exact-edge smoothing (moihgp_smooth_stream_exact): its per-latent tables, built lazily behind the smoother's (ensure_edges); the largest
+    // HEAD + TAIL of a latent they hold, read once per parameter set; and the buffer its calls share, kept on the handle: s[0] [L][d] and, where
+    // some latent's edges overlap in the call's T ticks, row 0 of Ps_t [L][T][d] (edge_ev marks the end of the last call that used it)
+    LazyTables et;
+    size_t edge_span = 0;
+    unsigned long long edge_span_version = 0;
+    void* dedge = nullptr; size_t edge_cap = 0;
+    hipStream_t edge_last = nullptr;
+    hipEvent_t edge_ev = nullptr;
+    bool edge_ev_set = false;
     // multi-horizon forecasts (moihgp_forecast_stream): the per-call tables (fp64 and fp32 copy), rebuilt by every call for its horizons
     CallTables fc;
     int opt_forecast_path = -1;          // option "forecast_path": -1 automatic, 0 scan kernel, 1 serial fp64
@@ -168,7 +178,7 @@ struct moihgp_gp {
 
 static void gp_free(moihgp_gp* g) {
     if (!g) return;
-    void* ptrs[] = {g->dU, g->dS, g->dsqrtS, g->dinvsqrtS, g->dsigma, g->dparams, g->cb64, g->cb32, g->dx, g->dpart, g->dTy, g->dUty, g->dTyhat, g->dloss, g->dgrad, g->dscratch, g->dwork, g->dpolar, g->dfallback, g->dwin, g->dunstable, g->dxscratch, g->cbd64, g->dU32, g->dhp, g->dlink, g->dwinmiss, g->dtp64, g->dtp32, g->dxc64, g->dxc32, g->dlinkflags, g->dgap, g->drescue_idx, g->drescue, g->drescue_const, g->sm.d, g->fc.d64, g->fc.d32, g->sp.d, g->lt.d64, g->itp.d64, g->slt.d64};
+    void* ptrs[] = {g->dU, g->dS, g->dsqrtS, g->dinvsqrtS, g->dsigma, g->dparams, g->cb64, g->cb32, g->dx, g->dpart, g->dTy, g->dUty, g->dTyhat, g->dloss, g->dgrad, g->dscratch, g->dwork, g->dpolar, g->dfallback, g->dwin, g->dunstable, g->dxscratch, g->cbd64, g->dU32, g->dhp, g->dlink, g->dwinmiss, g->dtp64, g->dtp32, g->dxc64, g->dxc32, g->dlinkflags, g->dgap, g->drescue_idx, g->drescue, g->drescue_const, g->sm.d, g->fc.d64, g->fc.d32, g->sp.d, g->lt.d64, g->itp.d64, g->slt.d64, g->et.d, g->dedge};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (void* p : g->pinned) (void)hipHostUnregister(p);
@@ -178,7 +188,7 @@ static void gp_free(moihgp_gp* g) {
     if (g->hflag) (void)hipHostFree(g->hflag);
     for (hipEvent_t e : g->prof_ev) (void)hipEventDestroy(e);
     if (g->order_ev) (void)hipEventDestroy(g->order_ev);
-    for (hipEvent_t e : {g->sm.ev, g->fc.ev, g->sp.ev, g->lt.ev, g->itp.ev, g->slt.ev})
+    for (hipEvent_t e : {g->sm.ev, g->fc.ev, g->sp.ev, g->lt.ev, g->itp.ev, g->slt.ev, g->et.ev, g->edge_ev})
         if (e) (void)hipEventDestroy(e);
     if (g->stream) (void)hipStreamDestroy(g->stream);
     delete g;
@@ -1183,6 +1193,76 @@ int moihgp_get_smoother(moihgp_gp* gp, size_t l, double* P, double* K, double* G
 }
 int moihgp_latent_variances(moihgp_gp* gp, double* var_filtered, double* var_smoothed) {
     return guard_rc([&] { return latent_variances_impl(gp, var_filtered, var_smoothed); });
+}
+
+// ---- exact-edge smoothing (edges.hip) ------------------------------------------------------------------------------------------------------------
+// The edge tables follow the smoother's, by the same protocol (ensure_tables).  The first call after a table rewrite also reads them once (it
+// synchronises): the largest HEAD + TAIL of a latent says whether a call of T ticks needs the scratch rows at all.
+static int ensure_edges(moihgp_gp* g, hipStream_t s, std::vector<double>* blocks = nullptr) {
+    if (int rc = ensure_smoother(g, s)) return rc;
+    const size_t block = (size_t)et_size(g->d);
+    ensure_tables(g, g->et, block, s, [&] { launch_edge_tables(kernel_base(g->kernel), g->d, g->cb64, g->sm.d, g->L, g->et.d, s); });
+    if (g->edge_span_version == g->cb_version && !blocks) return 0;
+    std::vector<double> b = read_tables(g, g->et, block, 0, g->L);
+    size_t span = 0;
+    dispatch_dim(g->d, [&](auto dim) {
+        using E = ET<decltype(dim)::value>;
+        for (size_t l = 0; l < g->L; l++)
+            if (b[l * block + E::STATUS] == 0.0) span = std::max(span, (size_t)b[l * block + E::HEAD] + (size_t)b[l * block + E::TAIL]);
+    });
+    g->edge_span = span;
+    g->edge_span_version = g->cb_version;
+    if (blocks) *blocks = std::move(b);
+    return 0;
+}
+
+static int smooth_stream_exact_impl(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, void* x, void* ys, void* var, size_t ld_out,
+                                    int* status, void* stream) {
+    if (int rc = check_sweep_call(gp, dtype, Ty, T, ld_in, x, x)) return rc;
+    // the sweeps start from the prior: x is zeroed and serves as their start state too
+    const SweepIo io = stream_sweep_io(gp, dtype, Ty, T, ld_in, x, x, ys, ld_out, stream);
+    if (var) {
+        if (int rc = check_outputs(io, {{ys, "ysmooth", "ysmooth"}, {var, "var", "var"}})) return rc;
+    } else {
+        if (int rc = check_outputs(io, {{ys, "ysmooth", "ysmooth"}})) return rc;
+    }
+    if (int rc = ensure_edges(gp, io.stream)) return rc;
+    note_user_stream(gp, io.stream);
+    const size_t d = (size_t)gp->d, es = dtype == MOIHGP_F64 ? 8 : 4;
+    const bool rows = gp->edge_span > T && T <= (size_t)kEdgeScratchTicks && T > 0;
+    if (!gp->edge_ev) MOIHGP_HIP_FATAL(hipEventCreateWithFlags(&gp->edge_ev, hipEventDisableTiming));
+    if (gp->edge_ev_set && io.stream != gp->edge_last) MOIHGP_HIP_FATAL(hipStreamWaitEvent(io.stream, gp->edge_ev, 0));
+    grow_device_buffer(gp->dedge, gp->edge_cap, sizeof(double) * gp->L * d * (1 + (rows ? T : 0)));
+    double* s0 = static_cast<double*>(gp->dedge);
+    MOIHGP_HIP_FATAL(hipMemsetAsync(x, 0, gp->L * d * es, io.stream));
+    launch_smooth_stream(gp->d, io, gp->sm.d, status, gp->opt_smoother_path, s0);
+    launch_smooth_edges(gp->d, io, gp->sm.d, gp->et.d, s0, rows ? s0 + gp->L * d : nullptr, var, status);
+    gp->edge_last = io.stream;
+    gp->edge_ev_set = true;
+    MOIHGP_HIP_FATAL(hipEventRecord(gp->edge_ev, io.stream));
+    return 0;
+}
+
+static int edge_lengths_impl(moihgp_gp* gp, int* head, int* tail) {
+    if (!gp) { set_last_error("null handle"); return 1; }
+    std::vector<double> b;
+    if (int rc = ensure_edges(gp, gp->stream, &b)) return rc;
+    dispatch_dim(gp->d, [&](auto dim) {
+        using E = ET<decltype(dim)::value>;
+        for (size_t l = 0; l < gp->L; l++) {
+            if (head) head[l] = (int)b[l * E::SIZE + E::HEAD];
+            if (tail) tail[l] = (int)b[l * E::SIZE + E::TAIL];
+        }
+    });
+    return 0;
+}
+
+int moihgp_smooth_stream_exact(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, void* x, void* ysmooth, void* var, size_t ld_out,
+                               int* status, void* stream) {
+    return guard_rc([&] { return smooth_stream_exact_impl(gp, dtype, Ty, T, ld_in, x, ysmooth, var, ld_out, status, stream); });
+}
+int moihgp_edge_lengths(moihgp_gp* gp, int* head, int* tail) {
+    return guard_rc([&] { return edge_lengths_impl(gp, head, tail); });
 }
 
 // ---- multi-horizon forecasts (forecast.hip) -----------------------------------------------------------------------------------------------------

@@ -241,7 +241,14 @@ struct SweepPlanes {
 };
 // io.yhat: the smoothed means ysmooth.  path: -1 automatic (scan kernels for the latents that pass the growth bound), 0 scan kernels, 1 serial fp64
 // for every latent
-void launch_smooth_stream(int d, const SweepIo& io, const double* tabs, int* status, int path);
+// s0 (or NULL): fp64 [L][d], receives the state s[0] the backward sweep holds when it leaves tick 0 (latents whose DARE failed: not written)
+void launch_smooth_stream(int d, const SweepIo& io, const double* tabs, int* status, int path, double* s0 = nullptr);
+// edges.hip: exact-edge smoothing (include/moihgp.h moihgp_smooth_stream_exact).  Per-latent fp64 block ET<D> of et_size(d) doubles (stream_tables.h) from
+// the model (cb64) and the smoother's blocks sm.  launch_smooth_edges runs behind launch_smooth_stream from a zero start state with its s0: it corrects
+// the head of the rows of io.yhat and of io.x, writes var (or NULL) and the status words 3 and 4.  scratch: [L][T][d] doubles, or NULL when no latent's
+// edges overlap in T ticks.
+void launch_edge_tables(int kernel, int d, const double* cb64, const double* sm, size_t L, double* et, hipStream_t stream);
+void launch_smooth_edges(int d, const SweepIo& io, const double* sm, const double* et, const double* s0, double* scratch, void* var, int* status);
 // the smoother's forward sweep alone, for the fixed-lag smoother: predicted means into io.yhat, and into io.x the filtered state after tick
 // T_state - 1 (T_state <= T; 0: io.xin), for the latents the scan kernels take (and the NaN row and state of a failed one)
 void launch_smooth_forward(int d, const SweepIo& io, const double* tabs, size_t T_state, int path);

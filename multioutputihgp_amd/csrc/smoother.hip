@@ -24,6 +24,8 @@
 //   smooth_serial_kernel     one lane per latent, fp64, tick by tick: the latents the scan kernels leave (growth bound failed, option
 //                            "smoother_path" = 1), and the status word of every latent.  The NaN row of a latent whose DARE did not converge
 //                            is written by smooth_fwd_kernel (by this kernel when it walks every latent).
+// The S0 instances of the backward and the serial kernel also hand out s[0], the state the backward sweep holds when it leaves tick 0 (fp64 [L][d]):
+// exact-edge smoothing (edges.hip) corrects the head of the row from it.
 // Arithmetic is fp64 throughout; fp32 streams are widened on load and narrowed on store.  The chunk-scan machinery of the two sweep kernels is
 // scan_sweep.h (shared with forecast.hip and sampler.hip; the backward chunk response is its chunk_response_bwd), the block layout SM<D>
 // stream_tables.h, the Stein solve (stein_solve) and the chunk powers of the tables kernel stationary_common.h.
@@ -92,9 +94,10 @@ __global__ void __launch_bounds__(64) smooth_fwd_kernel(const Tv* __restrict__ T
         for (int i = 0; i < D; i++) x_out[l * D + i] = (Tv)xseg[i];
 }
 
-template <typename Tv, int D>
+// S0 (exact-edge smoothing, edges.hip): s0 [L][D] receives the state s[0] the sweep holds when it leaves tick 0.  A smooth is the instance without it.
+template <typename Tv, int D, bool S0>
 __global__ void __launch_bounds__(64) smooth_bwd_kernel(const Tv* __restrict__ Ty, size_t T, size_t ld_in, const double* __restrict__ tabs,
-                                                        Tv* ys, size_t ld_out, int path) {
+                                                        Tv* ys, size_t ld_out, int path, double* s0) {
     using B = SM<D>;
     constexpr int NN = D * D;
     __shared__ double vb[kScanPlane];
@@ -145,12 +148,15 @@ __global__ void __launch_bounds__(64) smooth_bwd_kernel(const Tv* __restrict__ T
         stage_out(pb, prow, seg0, T, lane);
         __syncthreads();
     }
+    if (S0 && lane == 0)
+#pragma unroll
+        for (int i = 0; i < D; i++) s0[l * D + i] = sseg[i];
 }
 
 // Tick by tick, one lane per latent: the latents the scan kernels do not take, the NaN rows of latents whose DARE failed, every status word.
-template <typename Tv, int D>
+template <typename Tv, int D, bool S0>
 __global__ void __launch_bounds__(64) smooth_serial_kernel(const Tv* __restrict__ Ty, size_t T, size_t ld_in, const double* __restrict__ tabs, size_t L,
-                                                           const Tv* x_in, Tv* x_out, Tv* ys, size_t ld_out, int* status, int path) {
+                                                           const Tv* x_in, Tv* x_out, Tv* ys, size_t ld_out, int* status, int path, double* s0) {
     using B = SM<D>;
     constexpr int NN = D * D;
     const size_t l = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -182,6 +188,8 @@ __global__ void __launch_bounds__(64) smooth_serial_kernel(const Tv* __restrict_
         tick_step<double, D>(G, K, v, s);
         prow[t] = (Tv)(p + s[0]);
     }
+    if (S0)
+        for (int i = 0; i < D; i++) s0[l * D + i] = s[i];
 }
 
 }  // namespace
@@ -325,26 +333,29 @@ void launch_smoother_tables(int kernel, int d, const double* cb64, size_t L, dou
 }
 
 // The call's record is unpacked here, at the launch lines: forward and backward scan sweeps for the latents that take them, then the serial kernel
-// for the rest and the status words.
-template <typename Tv, int D>
-static void launch_smooth_t(const SweepIo& io, const double* tabs, int* status, int path) {
+// for the rest and the status words.  S0: the instances that hand out s[0] (exact-edge smoothing).
+template <typename Tv, int D, bool S0>
+static void launch_smooth_t(const SweepIo& io, const double* tabs, int* status, int path, double* s0) {
     const Tv *Ty = (const Tv*)io.Ty, *x_in = (const Tv*)io.xin;
     Tv *x = (Tv*)io.x, *ys = (Tv*)io.yhat;
     const size_t T = io.T, L = io.L;
     if (T > 0 && path != 1) {
         hipLaunchKernelGGL((smooth_fwd_kernel<Tv, D, false>), dim3((unsigned)L), dim3(64), 0, io.stream, Ty, T, io.ld, tabs, x_in, x, ys, io.ld_out, path, T);
         MOIHGP_HIP_FATAL(hipGetLastError());
-        hipLaunchKernelGGL((smooth_bwd_kernel<Tv, D>), dim3((unsigned)L), dim3(64), 0, io.stream, Ty, T, io.ld, tabs, ys, io.ld_out, path);
+        hipLaunchKernelGGL((smooth_bwd_kernel<Tv, D, S0>), dim3((unsigned)L), dim3(64), 0, io.stream, Ty, T, io.ld, tabs, ys, io.ld_out, path, s0);
         MOIHGP_HIP_FATAL(hipGetLastError());
     }
-    hipLaunchKernelGGL((smooth_serial_kernel<Tv, D>), dim3((unsigned)((L + 63) / 64)), dim3(64), 0, io.stream, Ty, T, io.ld, tabs, L, x_in, x, ys, io.ld_out,
-                       status, T > 0 ? path : 1);
+    hipLaunchKernelGGL((smooth_serial_kernel<Tv, D, S0>), dim3((unsigned)((L + 63) / 64)), dim3(64), 0, io.stream, Ty, T, io.ld, tabs, L, x_in, x, ys, io.ld_out,
+                       status, T > 0 ? path : 1, s0);
     MOIHGP_HIP_FATAL(hipGetLastError());
 }
 
-void launch_smooth_stream(int d, const SweepIo& io, const double* tabs, int* status, int path) {
+void launch_smooth_stream(int d, const SweepIo& io, const double* tabs, int* status, int path, double* s0) {
     if (io.L == 0) return;
-    dispatch_stream(d, io.dtype, [&](auto tv, auto dim) { launch_smooth_t<decltype(tv), decltype(dim)::value>(io, tabs, status, path); });
+    dispatch_stream(d, io.dtype, [&](auto tv, auto dim) {
+        if (s0) launch_smooth_t<decltype(tv), decltype(dim)::value, true>(io, tabs, status, path, s0);
+        else launch_smooth_t<decltype(tv), decltype(dim)::value, false>(io, tabs, status, path, nullptr);
+    });
 }
 
 void launch_smooth_forward(int d, const SweepIo& io, const double* tabs, size_t T_state, int path) {

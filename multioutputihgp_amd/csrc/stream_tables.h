@@ -1,4 +1,4 @@
-// stream_tables.h -- the per-latent table blocks of the whole-stream smoother (smoother.hip), forecasts (forecast.hip), fixed-lag smoother (lagged.hip), off-grid smoother (interp.hip) and sampler (sampler.hip), the
+// stream_tables.h -- the per-latent table blocks of the whole-stream smoother (smoother.hip), its exact edges (edges.hip), forecasts (forecast.hip), fixed-lag smoother (lagged.hip), off-grid smoother (interp.hip) and sampler (sampler.hip), the
 // chunk geometry their chunk powers are built for, and the (d, dtype) dispatch of their launchers.  Read by those files and by capi.cpp.
 #pragma once
 #include "common.h"
@@ -68,7 +68,22 @@ struct SP {
     static constexpr int SIZE = (STATUS + 1 + 1) / 2 * 2;
 };
 
+// per-latent edge block (fp64), offsets in doubles, next to the latent's SM<D> block (which holds G, P, PF, Ps): what exact-edge smoothing (edges.hip)
+// needs of the model beside it
+constexpr int kEdgeCap = 1 << 20;               // HEAD and TAIL are capped here; the cap means "never reached"
+constexpr int kEdgeScratchTicks = 4096;         // overlapping edges are walked in streams of at most this many ticks
+template <int D>
+struct ET {
+    static constexpr int NN = D * D;
+    static constexpr int E = 0;                                 // Pinf^-1 - P^-1
+    static constexpr int PSROW = E + NN;                        // [D] e0^T Ps
+    static constexpr int HEAD = PSROW + D, TAIL = HEAD + 1;     // the smallest n with |G^n|inf <= 2^-60, the smallest k with |G^k|inf^2 <= 2^-60 (as doubles)
+    static constexpr int STATUS = TAIL + 1;                     // 0 ok, 1 the Kalman DARE failed, 4 Pinf or P could not be inverted / something is not finite
+    static constexpr int SIZE = (STATUS + 1 + 1) / 2 * 2;
+};
+
 constexpr int sm_size(int d) { return d == 2 ? SM<2>::SIZE : SM<3>::SIZE; }
+constexpr int et_size(int d) { return d == 2 ? ET<2>::SIZE : ET<3>::SIZE; }
 constexpr int fc_size(int d) { return d == 2 ? FT<2>::SIZE : FT<3>::SIZE; }
 constexpr int sp_size(int d) { return d == 2 ? SP<2>::SIZE : SP<3>::SIZE; }
 constexpr int lt_size(int d) { return d == 2 ? LT<2>::SIZE : LT<3>::SIZE; }

@@ -419,6 +419,44 @@ class LatentBank:
         _check(rc, self._lib)
         return ysmooth, x, status
 
+    def smooth_exact(self, Ty: torch.Tensor, T: Optional[int] = None, x: Optional[torch.Tensor] = None, ysmooth: Optional[torch.Tensor] = None,
+                     var: Optional[torch.Tensor] = None, want_var: bool = True, stream=None):
+        """Exact-edge smoothing of T ticks for every latent (include/moihgp.h moihgp_smooth_stream_exact): `smooth` from the prior (a zero start
+        state), corrected at the head of the stream for the model's own prior on the first state, with the posterior variance of the latent
+        function at every tick.  For a gap-free stream this is the GP posterior at every tick, for any T >= 1.
+
+        Returns (ysmooth [L, >=T], var [L, >=T] or None, x [L, d] end state, status [L] int32: 0 ok, 1 DARE not converged (rows NaN), 3 the
+        latent's edges overlap in a stream longer than 4096 ticks, 4 its edge tables failed (3, 4: the row and x are `smooth`'s, var is
+        var_smoothed)).  Asynchronous on the current torch stream, but for the first call after an update, which reads the edge lengths back.
+        `x` receives the end state (it is not a start state).  `ysmooth` and `var` (optional) must not overlap Ty or each other and share one row
+        stride, which may differ from the stream's; `want_var=False` (with no `var`) writes no variance."""
+        T, ld = self._check_stream(Ty, T)
+        self._refuse_stacked("smooth_exact")
+        x, _ = self._start_state(Ty, x, None)
+        if ysmooth is None and var is not None:
+            ld_out = _row_stride("var", var, T, Ty)
+            ysmooth = torch.empty((self.L, ld_out), dtype=Ty.dtype, device=Ty.device)[:, :T]
+        ysmooth, ld_out = self._ysmooth_buffer(Ty, T, ysmooth)
+        if var is None and want_var:
+            var = torch.empty((self.L, ld_out), dtype=Ty.dtype, device=Ty.device)[:, :T]
+        if var is not None and _row_stride("var", var, T, Ty) != ld_out:
+            raise ValueError("var and ysmooth must have the same row stride")
+        status = torch.empty((self.L,), dtype=torch.int32, device=Ty.device)
+        rc = self._lib.moihgp_smooth_stream_exact(self._h, _DT[Ty.dtype], C.c_void_p(Ty.data_ptr()), T, ld, C.c_void_p(x.data_ptr()),
+                                                  C.c_void_p(ysmooth.data_ptr()), C.c_void_p(var.data_ptr()) if var is not None else None, ld_out,
+                                                  C.c_void_p(status.data_ptr()), _stream_ptr(stream))
+        _check(rc, self._lib)
+        return ysmooth, var, x, status
+
+    def edge_lengths(self):
+        """(head [L], tail [L]) of every latent (moihgp_edge_lengths), int numpy arrays: `smooth_exact` touches the ticks before `head` and the
+        last `tail` ticks of a row; 2^20 means "never reached"."""
+        self._refuse_stacked("edge_lengths")
+        head, tail = np.zeros(self.L, dtype=np.int32), np.zeros(self.L, dtype=np.int32)
+        ip = C.POINTER(C.c_int)
+        _check(self._lib.moihgp_edge_lengths(self._h, head.ctypes.data_as(ip), tail.ctypes.data_as(ip)), self._lib)
+        return head, tail
+
     def smoother(self, l: int) -> dict:
         """The smoother's stationary quantities of latent l (moihgp_get_smoother): P (Kalman DARE), K, G, Ps, var_filtered, var_smoothed."""
         d = self.d
@@ -857,6 +895,29 @@ def smooth_outputs(gp, Y: torch.Tensor, stream=None):
     bad = int((status != 0).sum())      # (synchronises)
     return Ys, _output_variances(gp, bank.latent_variances()[1], bad, f"smooth_outputs: the Kalman DARE of {bad} latent(s) did not converge; their rows "
                                  "are NaN and so is every output that mixes them")
+
+
+def smooth_outputs_exact(gp, Y: torch.Tensor, var_ticks=(0, -1), stream=None):
+    """`smooth_outputs` with exact edges (LatentBank.smooth_exact): project_stream -> smooth_exact -> unproject_stream, from the prior.
+
+    Returns (Ys [T, M] in Y's dtype, var_Y [len(var_ticks), M] fp64 numpy) with var_Y[k, m] = sum_l U[m, l]^2 S_l var[l, var_ticks[k]]: the
+    posterior variance of the latent FUNCTION at output m and tick var_ticks[k] (negative ticks count from the end), without the observation
+    noise.  For a gap-free series both are the GP posterior's at every tick.  Raises MoihgpError on any non-zero status (1 the Kalman DARE did
+    not converge, 3 a latent's edges overlap in a series longer than 4096 ticks, 4 its edge tables failed).  Missing outputs are projected as
+    in smooth_outputs."""
+    T = Y.shape[0]
+    ticks = [int(t) for t in var_ticks]
+    if any(t < -T or t >= T for t in ticks):
+        raise ValueError("var_ticks must lie in -T .. T - 1")
+    bank = LatentBank.from_handle(gp)
+    Ty = project_stream(gp, Y, stream=stream)
+    ys, var, _, status = bank.smooth_exact(Ty, T=T, stream=stream)
+    Ys = unproject_stream(gp, ys, T, stream=stream)
+    with torch.cuda.stream(torch.cuda.current_stream() if stream is None else stream):
+        picked = var[:, ticks].to(torch.float64).T.contiguous().cpu().numpy() if ticks else np.zeros((0, bank.L))     # (synchronises)
+        bad = int((status != 0).sum())
+    return Ys, _output_variances(gp, picked, bad, f"smooth_outputs_exact: {bad} latent(s) have a non-zero status (1 Kalman DARE not converged, 3 edges "
+                                 "overlap in a series longer than 4096 ticks, 4 edge tables failed)")
 
 
 def sample_noise(seed: int, L: int, S: int, T: int, latent0: int = 0, sample0: int = 0, want_start: bool = True, device="cuda", stream=None):

@@ -3,7 +3,9 @@
 Prints one line per (dtype, cache state) with the event-timed duration of a whole smooth call (forward + backward + the small status kernel)
 and the algorithmic traffic of its stream passes (forward: read y, write p; backward: read y, read p, write ys).  "cold" evicts the caches
 between calls by writing a 2 GB buffer; "resident" repeats the call on the same buffers.  Run under `rocprofv3 --kernel-trace --stats` for the
-per-kernel split (smooth_fwd_kernel, smooth_bwd_kernel, smoother_tables_kernel: --rebuild forces one table build per call)."""
+per-kernel split (smooth_fwd_kernel, smooth_bwd_kernel, smoother_tables_kernel: --rebuild forces one table build per call).
+--exact adds two legs per (dtype, cache state): exact-edge smoothing (moihgp_smooth_stream_exact) without and with the variance rows, beside the
+smooth call they extend, and the time of one stream-sized plane write (a fill) to hold the extra against."""
 import argparse
 import os
 import sys
@@ -21,6 +23,7 @@ def main():
     ap.add_argument("--T", type=int, default=10000)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--path", type=int, default=-1, help='option "smoother_path": -1 automatic, 0 scan kernels, 1 serial fp64')
+    ap.add_argument("--exact", action="store_true", help="also time smooth_exact without and with var, and one plane write")
     ap.add_argument("--rebuild", action="store_true", help="rewrite the tables before every call (times the tables kernel too)")
     a = ap.parse_args()
     torch.cuda.set_device(0)
@@ -37,9 +40,17 @@ def main():
         _, _, status = bank.smooth(Ty, x=x, ysmooth=ys)
         torch.cuda.synchronize()
         vf, vs = bank.latent_variances()
+        var = torch.empty_like(Ty)
+        legs = [("smooth", lambda: bank.smooth(Ty, x=x, ysmooth=ys))]
+        if a.exact:
+            head, tail = bank.edge_lengths()
+            print(f"edge lengths: head {head.min()} .. {head.max()}, tail {tail.min()} .. {tail.max()}")
+            legs += [("smooth_exact, no var", lambda: bank.smooth_exact(Ty, x=x, ysmooth=ys, want_var=False)),
+                     ("smooth_exact, var", lambda: bank.smooth_exact(Ty, x=x, ysmooth=ys, var=var)),
+                     ("one plane write", lambda: var.fill_(1.0))]
         print(f"status != 0: {int((status != 0).sum())} latents; var_smoothed / var_filtered in [{np.min(vs / vf):.3f}, {np.max(vs / vf):.3f}]")
         mb = a.L * a.T * es / 1e6
-        for cold in (False, True):
+        for cold, (name, call) in [(c, leg) for c in (False, True) for leg in legs]:
             ts = []
             for _ in range(a.iters):
                 if a.rebuild:
@@ -48,13 +59,13 @@ def main():
                     flush.fill_(1.0)
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
-                bank.smooth(Ty, x=x, ysmooth=ys)
+                call()
                 e1.record()
                 torch.cuda.synchronize()
                 ts.append(e0.elapsed_time(e1))
             t = float(np.median(ts)) * 1e3
-            print(f"smooth {str(dt).split('.')[-1]} L={a.L} T={a.T} {'cold' if cold else 'resident'}: {t:.1f} us  "
-                  f"(traffic {2 * mb:.0f} MB + {3 * mb:.0f} MB -> {5 * mb * 1e6 / (t * 1e-6) / 1e12:.2f} TB/s)", flush=True)
+            traffic = f"  (traffic {2 * mb:.0f} MB + {3 * mb:.0f} MB -> {5 * mb * 1e6 / (t * 1e-6) / 1e12:.2f} TB/s)" if name == "smooth" else ""
+            print(f"{name} {str(dt).split('.')[-1]} L={a.L} T={a.T} {'cold' if cold else 'resident'}: {t:.1f} us{traffic}", flush=True)
 
 
 if __name__ == "__main__":
