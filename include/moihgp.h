@@ -302,6 +302,35 @@ int moihgp_smooth_stream_exact(moihgp_gp* gp, int dtype, const void* Ty, size_t 
                                int* status, void* stream);
 int moihgp_edge_lengths(moihgp_gp* gp, int* head, int* tail);
 
+/* ---- exact smoothing across missing ticks: the GP posterior at every tick (not in the reference) ------------------------------------------
+ * Every other whole-stream estimator runs on steady-state gains, and moihgp_smooth_stream_exact corrects them at the two ends of a stream only:
+ * inside a gap its variance does not widen.  This entry runs the time-varying recursion instead.  Per latent, in fp64: A the handle's, Pinf the
+ * model's, Q = sym(Pinf - A Pinf A^T), H = e0^T, R the noise parameter; sym(X) = (X + X^T) / 2.  A NaN in Ty marks a missing tick, and nothing
+ * else does.
+ *     forward   xp[0] = 0, P[0] = Pinf;   t > 0: xp[t] = A xf[t-1],  P[t] = sym(A PF[t-1] A^T + Q)
+ *               observed: S = P[t]_00 + R, v = y[t] - xp[t]_0, K = P[t] e0 / S, xf[t] = xp[t] + K v, PF[t] = sym(P[t] - K (e0^T P[t]))
+ *                         nll += (log(2 pi S) + v^2 / S) / 2
+ *               missing:  xf[t] = xp[t], PF[t] = P[t]
+ *     backward  xs[T-1] = xf[T-1], Ps[T-1] = PF[T-1]
+ *               G = PF[t] A^T P[t+1]^-1      (pivoted elimination, not Cholesky: Q is indefinite for Matern-5/2)
+ *               xs[t] = xf[t] + G (xs[t+1] - xp[t+1]),  Ps[t] = sym(PF[t] + G (Ps[t+1] - P[t+1]) G^T)
+ *     outputs   mean[t] = xs[t]_0,  var[t] = Ps[t]_00 (the latent FUNCTION, no noise),  x = xf[T-1],  P_end = PF[T-1],  nll
+ * For any pattern of missing ticks mean and var are the GP posterior given the observed ticks, nll is -log N(y_obs; 0, C_oo + R I), and (x, P_end)
+ * is the filtering distribution at the last tick.  No DARE is involved, so the entry also serves latents whose Kalman DARE does not converge.
+ * An all-missing row gives mean 0, var Pinf_00 and nll 0.  T = 0: nothing is written to the rows, x = 0, P_end = Pinf, nll = 0.
+ * status per latent: 0 ok; 5 the recursion broke down (S <= 0, a pivot of P[t+1] was zero, or a non-finite quantity arose -- a +-Inf
+ * observation among them): the latent's mean and var rows, x, P_end and nll are NaN, no other latent is affected.  Codes 1 to 4 keep their
+ * meanings and do not occur here.
+ * moihgp_posterior_stream: Ty, ld_in, mean, ld_out, alignment, overlap rules, asynchrony and stream bookkeeping as moihgp_smooth_stream_exact
+ *   (mean in ysmooth's place).  x [L][d] (dtype) receives the end state: an output only, the start is the prior.  P_end: DEVICE fp64 [L][d*d] or
+ *   NULL.  var [L][ld_out] (dtype) or NULL: shape and rules as mean, may overlap neither Ty nor mean.  nll: DEVICE fp64 [L] or NULL.  status:
+ *   DEVICE int [L] or NULL.  The arithmetic is fp64 for both stream dtypes.  Series-major only.  Stacked models: 3.
+ *   Scratch: one buffer on the handle, grown on demand (a failed allocation returns 2 with the message; nothing falls back):
+ *       8 * ((d + d (d + 1) / 2) * ceil(T / 16) + 1) * L bytes
+ *   -- a checkpoint (xf, upper triangle of PF) every 16 ticks, 4.5 bytes per tick and latent at d = 3, and one word per latent. */
+int moihgp_posterior_stream(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, void* x, double* P_end, void* mean, void* var,
+                            size_t ld_out, double* nll, int* status, void* stream);
+
 /* ---- multi-horizon forecasts of whole streams, with variances (not in the reference, whose only route is the per-tick ABI: one step(x, y) and
  * then h prediction-only step(x) calls per tick and per horizon, ihgp.h:96-100) --------------------------------------------------------------
  * Per latent, A the handle's A, H = e0, and gains (K, M):

@@ -165,6 +165,46 @@ public:
         }
         return Ys;
     }
+    // (not in the reference) The GP posterior across missing ticks (include/moihgp.h moihgp_posterior_stream): the posterior mean of every output at
+    // every tick given ALL of Y, by the time-varying Kalman recursion from the model's own prior, with no update at a missing tick -- exact for
+    // any pattern of wholly missing ticks, where predictSmoothed() and predictSmoothedExact() run on steady-state gains.  varY (if not null)
+    // receives, per entry of `ticks` (negative: counted from the end), the posterior variance of the latent FUNCTION behind every output at that
+    // tick, without the observation noise: (*varY)[k][m] = sum_l U[m][l]^2 S_l var[l][ticks[k]]; it widens inside a gap.  nll (if not null)
+    // receives the latents' exact -log marginal likelihoods of their projected series [L].  fp64 on the device: project_stream ->
+    // posterior_stream -> unproject_stream.  Throws std::invalid_argument for a tick outside -T .. T - 1 and std::runtime_error on a non-zero
+    // status (5: a latent's recursion broke down).  Missing outputs (NaN) are projected as in predictSmoothed().
+    std::vector<Vector> predictPosterior(const std::vector<Vector>& Y, const std::vector<long>& ticks = std::vector<long>(),
+                                         std::vector<Vector>* varY = nullptr, Vector* nll = nullptr) {
+        const size_t T = Y.size(), L = _num_latent, M = _num_output, ld = (T + 1) / 2 * 2;
+        for (long t : ticks)
+            if (t < -(long)T || t >= (long)T) throw std::invalid_argument("predictPosterior: ticks must lie in -T .. T - 1");
+        if (varY) varY->assign(ticks.size(), Vector(M, 0.0));
+        if (nll) nll->assign(L, 0.0);
+        if (T == 0) return std::vector<Vector>();
+        Vector var(varY ? L * ld : 0);
+        std::vector<Vector> Ys = streamRoundTrip("predictPosterior", Y, {L * ld, L * ld, L * ld, L}, [&](StreamTrip& d) {
+            int rc = d.project();
+            if (!rc) rc = moihgp_posterior_stream(d.h, MOIHGP_F64, d.buf[0], T, ld, d.x, nullptr, d.buf[1], varY ? d.buf[2] : nullptr, ld,
+                                                  nll ? d.buf[3] : nullptr, d.status, d.s);
+            if (!rc && varY) rc = moihgp_dvec_download(d.ctx, var.data(), d.buf[2], L * ld);
+            if (!rc && nll) rc = moihgp_dvec_download(d.ctx, nll->data(), d.buf[3], L);
+            return rc ? rc : d.fetch(d.buf[1]);
+        }, [](size_t l, int status) {
+            return "latent " + std::to_string(l) + " has status " + std::to_string(status) + " (its recursion broke down)";
+        })[0];
+        if (varY) {
+            const Vector prm = _moihgp->getParams();                 // [U row-major | S | ...]
+            for (size_t k = 0; k < ticks.size(); k++) {
+                const size_t t = (size_t)(ticks[k] < 0 ? ticks[k] + (long)T : ticks[k]);
+                for (size_t m = 0; m < M; m++) {
+                    double a = 0.0;
+                    for (size_t l = 0; l < L; l++) a += prm[m * L + l] * prm[m * L + l] * (prm[M * L + l] * var[l * ld + t]);
+                    (*varY)[k][m] = a;
+                }
+            }
+        }
+        return Ys;
+    }
     // (not in the reference) Seeded joint posterior samples of the whole series with the current parameters (include/moihgp.h
     // moihgp_sample_stream): element [s][t] is sample s of every output at tick t given ALL of Y -- the smoothed mean of predictSmoothed() plus a
     // draw of the steady-state deviation process (exact covariance in the interior of a long gap-free series, under-dispersed near its ends and

@@ -24,7 +24,7 @@ ADDITIVE_SYMBOLS = [
     "moihgp_profile_enable", "moihgp_profile_stride", "moihgp_profile_read", "moihgp_window_set", "moihgp_window_eval", "moihgp_pin_host_buffer",
     "moihgp_update_dev", "moihgp_window_eval_dev", "moihgp_update_dev_on", "moihgp_window_eval_dev_on", "moihgp_get_params_dev", "moihgp_set_option", "moihgp_release_stream",
     "moihgp_ls_shard_gram", "moihgp_ls_shard_apply", "moihgp_smooth_stream", "moihgp_get_smoother", "moihgp_latent_variances",
-    "moihgp_smooth_stream_exact", "moihgp_edge_lengths",
+    "moihgp_smooth_stream_exact", "moihgp_edge_lengths", "moihgp_posterior_stream",
     "moihgp_forecast_stream", "moihgp_forecast_tail", "moihgp_forecast_variances", "moihgp_forecast_scores",
     "moihgp_lagged_stream", "moihgp_lagged_variances",
     "moihgp_interp_stream", "moihgp_interp_variances",
@@ -163,6 +163,9 @@ def load_library():
                                                C.c_void_p, C.c_void_p]
     lib.moihgp_edge_lengths.restype = C.c_int
     lib.moihgp_edge_lengths.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.moihgp_posterior_stream.restype = C.c_int
+    lib.moihgp_posterior_stream.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]
     lib.moihgp_forecast_stream.restype = C.c_int
     lib.moihgp_forecast_stream.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_size_t,
                                            C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]

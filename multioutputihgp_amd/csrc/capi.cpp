@@ -157,6 +157,13 @@ struct moihgp_gp {
     hipStream_t edge_last = nullptr;
     hipEvent_t edge_ev = nullptr;
     bool edge_ev_set = false;
+    // exact smoothing across missing ticks (moihgp_posterior_stream): its per-latent model blocks, built lazily, and the scratch its calls share, kept
+    // on the handle and grown on demand: the forward walk's checkpoints and breakdown flags (post_ev marks the end of the last call that used it)
+    LazyTables pt;
+    void* dpost = nullptr; size_t post_cap = 0;
+    hipStream_t post_last = nullptr;
+    hipEvent_t post_ev = nullptr;
+    bool post_ev_set = false;
     // multi-horizon forecasts (moihgp_forecast_stream): the per-call tables (fp64 and fp32 copy), rebuilt by every call for its horizons
     CallTables fc;
     int opt_forecast_path = -1;          // option "forecast_path": -1 automatic, 0 scan kernel, 1 serial fp64
@@ -178,7 +185,7 @@ struct moihgp_gp {
 
 static void gp_free(moihgp_gp* g) {
     if (!g) return;
-    void* ptrs[] = {g->dU, g->dS, g->dsqrtS, g->dinvsqrtS, g->dsigma, g->dparams, g->cb64, g->cb32, g->dx, g->dpart, g->dTy, g->dUty, g->dTyhat, g->dloss, g->dgrad, g->dscratch, g->dwork, g->dpolar, g->dfallback, g->dwin, g->dunstable, g->dxscratch, g->cbd64, g->dU32, g->dhp, g->dlink, g->dwinmiss, g->dtp64, g->dtp32, g->dxc64, g->dxc32, g->dlinkflags, g->dgap, g->drescue_idx, g->drescue, g->drescue_const, g->sm.d, g->fc.d64, g->fc.d32, g->sp.d, g->lt.d64, g->itp.d64, g->slt.d64, g->et.d, g->dedge};
+    void* ptrs[] = {g->dU, g->dS, g->dsqrtS, g->dinvsqrtS, g->dsigma, g->dparams, g->cb64, g->cb32, g->dx, g->dpart, g->dTy, g->dUty, g->dTyhat, g->dloss, g->dgrad, g->dscratch, g->dwork, g->dpolar, g->dfallback, g->dwin, g->dunstable, g->dxscratch, g->cbd64, g->dU32, g->dhp, g->dlink, g->dwinmiss, g->dtp64, g->dtp32, g->dxc64, g->dxc32, g->dlinkflags, g->dgap, g->drescue_idx, g->drescue, g->drescue_const, g->sm.d, g->fc.d64, g->fc.d32, g->sp.d, g->lt.d64, g->itp.d64, g->slt.d64, g->et.d, g->dedge, g->pt.d, g->dpost};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (void* p : g->pinned) (void)hipHostUnregister(p);
@@ -188,7 +195,7 @@ static void gp_free(moihgp_gp* g) {
     if (g->hflag) (void)hipHostFree(g->hflag);
     for (hipEvent_t e : g->prof_ev) (void)hipEventDestroy(e);
     if (g->order_ev) (void)hipEventDestroy(g->order_ev);
-    for (hipEvent_t e : {g->sm.ev, g->fc.ev, g->sp.ev, g->lt.ev, g->itp.ev, g->slt.ev, g->et.ev, g->edge_ev})
+    for (hipEvent_t e : {g->sm.ev, g->fc.ev, g->sp.ev, g->lt.ev, g->itp.ev, g->slt.ev, g->et.ev, g->edge_ev, g->pt.ev, g->post_ev})
         if (e) (void)hipEventDestroy(e);
     if (g->stream) (void)hipStreamDestroy(g->stream);
     delete g;
@@ -1263,6 +1270,35 @@ int moihgp_smooth_stream_exact(moihgp_gp* gp, int dtype, const void* Ty, size_t 
 }
 int moihgp_edge_lengths(moihgp_gp* gp, int* head, int* tail) {
     return guard_rc([&] { return edge_lengths_impl(gp, head, tail); });
+}
+
+// ---- exact smoothing across missing ticks (posterior.hip) ------------------------------------------------------------------------------------------
+// No DARE and no smoother tables: the model blocks alone, by the protocol of the other lazy tables.  The scratch is the handle's, as dedge is.
+static int posterior_stream_impl(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, void* x, double* P_end, void* mean, void* var,
+                                 size_t ld_out, double* nll, int* status, void* stream) {
+    if (int rc = check_sweep_call(gp, dtype, Ty, T, ld_in, x, x)) return rc;
+    const SweepIo io = stream_sweep_io(gp, dtype, Ty, T, ld_in, x, x, mean, ld_out, stream);
+    if (var) {
+        if (int rc = check_outputs(io, {{mean, "mean", "mean"}, {var, "var", "var"}})) return rc;
+    } else {
+        if (int rc = check_outputs(io, {{mean, "mean", "mean"}})) return rc;
+    }
+    if (kernel_stack(gp->kernel)) { set_last_error("posterior: stacked models are not supported (Matern-3/2 and -5/2 only)"); return 3; }
+    ensure_tables(gp, gp->pt, (size_t)pt_size(gp->d), io.stream, [&] { launch_posterior_tables(kernel_base(gp->kernel), gp->d, gp->cb64, gp->L, gp->pt.d, io.stream); });
+    note_user_stream(gp, io.stream);
+    if (!gp->post_ev) MOIHGP_HIP_FATAL(hipEventCreateWithFlags(&gp->post_ev, hipEventDisableTiming));
+    if (gp->post_ev_set && io.stream != gp->post_last) MOIHGP_HIP_FATAL(hipStreamWaitEvent(io.stream, gp->post_ev, 0));
+    grow_device_buffer(gp->dpost, gp->post_cap, sizeof(double) * post_scratch_doubles(gp->d, T, gp->L));
+    const int rc = launch_posterior_stream(gp->d, io, gp->pt.d, static_cast<double*>(gp->dpost), P_end, var, nll, status);
+    gp->post_last = io.stream;
+    gp->post_ev_set = true;
+    MOIHGP_HIP_FATAL(hipEventRecord(gp->post_ev, io.stream));
+    return rc;
+}
+
+int moihgp_posterior_stream(moihgp_gp* gp, int dtype, const void* Ty, size_t T, size_t ld_in, void* x, double* P_end, void* mean, void* var, size_t ld_out,
+                            double* nll, int* status, void* stream) {
+    return guard_rc([&] { return posterior_stream_impl(gp, dtype, Ty, T, ld_in, x, P_end, mean, var, ld_out, nll, status, stream); });
 }
 
 // ---- multi-horizon forecasts (forecast.hip) -----------------------------------------------------------------------------------------------------

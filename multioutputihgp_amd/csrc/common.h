@@ -249,6 +249,12 @@ void launch_smooth_stream(int d, const SweepIo& io, const double* tabs, int* sta
 // edges overlap in T ticks.
 void launch_edge_tables(int kernel, int d, const double* cb64, const double* sm, size_t L, double* et, hipStream_t stream);
 void launch_smooth_edges(int d, const SweepIo& io, const double* sm, const double* et, const double* s0, double* scratch, void* var, int* status);
+// posterior.hip: exact smoothing across missing ticks (include/moihgp.h moihgp_posterior_stream).  Per-latent fp64 block PT<D> of pt_size(d) doubles
+// (stream_tables.h) from the constant blocks cb64.  launch_posterior_stream: the forward and the backward kernel; io.yhat receives the means, io.x the
+// end state (io.xin is not read: the start is the prior); scratch: post_scratch_doubles(d, T, L) doubles; P_end, var, nll, status: or NULL.
+// Returns 0, or 2 with the last error set.
+void launch_posterior_tables(int kernel, int d, const double* cb64, size_t L, double* pt, hipStream_t stream);
+int launch_posterior_stream(int d, const SweepIo& io, const double* pt, double* scratch, double* P_end, void* var, double* nll, int* status);
 // the smoother's forward sweep alone, for the fixed-lag smoother: predicted means into io.yhat, and into io.x the filtered state after tick
 // T_state - 1 (T_state <= T; 0: io.xin), for the latents the scan kernels take (and the NaN row and state of a failed one)
 void launch_smooth_forward(int d, const SweepIo& io, const double* tabs, size_t T_state, int path);

@@ -1,4 +1,4 @@
-// stream_tables.h -- the per-latent table blocks of the whole-stream smoother (smoother.hip), its exact edges (edges.hip), forecasts (forecast.hip), fixed-lag smoother (lagged.hip), off-grid smoother (interp.hip) and sampler (sampler.hip), the
+// stream_tables.h -- the per-latent table blocks of the whole-stream smoother (smoother.hip), its exact edges (edges.hip), the exact posterior (posterior.hip), forecasts (forecast.hip), fixed-lag smoother (lagged.hip), off-grid smoother (interp.hip) and sampler (sampler.hip), the
 // chunk geometry their chunk powers are built for, and the (d, dtype) dispatch of their launchers.  Read by those files and by capi.cpp.
 #pragma once
 #include "common.h"
@@ -82,8 +82,26 @@ struct ET {
     static constexpr int SIZE = (STATUS + 1 + 1) / 2 * 2;
 };
 
+// per-latent model block (fp64), offsets in doubles: what the exact posterior (posterior.hip) walks with.  No DARE: the handle's A and the model's own
+// Pinf and R, and Q = sym(Pinf - A Pinf A^T)
+template <int D>
+struct PT {
+    static constexpr int NN = D * D;
+    static constexpr int A = 0, Q = A + NN, PINF = Q + NN, R = PINF + NN;
+    static constexpr int SIZE = (R + 1 + 1) / 2 * 2;
+};
+// The walk of posterior.hip: the forward kernel leaves a checkpoint (xf, PF) every kPostBlock ticks, the backward kernel recomputes a block from
+// it; both move the rows through LDS in tiles of kPostTile ticks (a multiple of kPostBlock).  A checkpoint holds xf and the upper triangle of PF.
+constexpr int kPostBlock = 16;
+constexpr int kPostTile = 32;
+constexpr int post_ckpt_doubles(int d) { return d + d * (d + 1) / 2; }
+// doubles of scratch a call of T ticks and L latents needs: the checkpoints [ceil(T / kPostBlock)][post_ckpt_doubles(d)][L], then one word per
+// latent (the forward walk's breakdown flag)
+constexpr size_t post_scratch_doubles(int d, size_t T, size_t L) { return ((T + kPostBlock - 1) / kPostBlock * (size_t)post_ckpt_doubles(d) + 1) * L; }
+
 constexpr int sm_size(int d) { return d == 2 ? SM<2>::SIZE : SM<3>::SIZE; }
 constexpr int et_size(int d) { return d == 2 ? ET<2>::SIZE : ET<3>::SIZE; }
+constexpr int pt_size(int d) { return d == 2 ? PT<2>::SIZE : PT<3>::SIZE; }
 constexpr int fc_size(int d) { return d == 2 ? FT<2>::SIZE : FT<3>::SIZE; }
 constexpr int sp_size(int d) { return d == 2 ? SP<2>::SIZE : SP<3>::SIZE; }
 constexpr int lt_size(int d) { return d == 2 ? LT<2>::SIZE : LT<3>::SIZE; }

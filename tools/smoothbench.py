@@ -5,7 +5,9 @@ and the algorithmic traffic of its stream passes (forward: read y, write p; back
 between calls by writing a 2 GB buffer; "resident" repeats the call on the same buffers.  Run under `rocprofv3 --kernel-trace --stats` for the
 per-kernel split (smooth_fwd_kernel, smooth_bwd_kernel, smoother_tables_kernel: --rebuild forces one table build per call).
 --exact adds two legs per (dtype, cache state): exact-edge smoothing (moihgp_smooth_stream_exact) without and with the variance rows, beside the
-smooth call they extend, and the time of one stream-sized plane write (a fill) to hold the extra against."""
+smooth call they extend, and the time of one stream-sized plane write (a fill) to hold the extra against.
+--posterior adds two legs: the exact posterior across missing ticks (moihgp_posterior_stream) with its variance rows and nll, on the gap-free
+stream and on a copy with 1 % of the ticks missing (posterior_fwd_kernel, posterior_bwd_kernel in a kernel trace)."""
 import argparse
 import os
 import sys
@@ -24,6 +26,7 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--path", type=int, default=-1, help='option "smoother_path": -1 automatic, 0 scan kernels, 1 serial fp64')
     ap.add_argument("--exact", action="store_true", help="also time smooth_exact without and with var, and one plane write")
+    ap.add_argument("--posterior", action="store_true", help="also time posterior() with var and nll, gap-free and with 1 %% of the ticks missing")
     ap.add_argument("--rebuild", action="store_true", help="rewrite the tables before every call (times the tables kernel too)")
     a = ap.parse_args()
     torch.cuda.set_device(0)
@@ -48,6 +51,11 @@ def main():
             legs += [("smooth_exact, no var", lambda: bank.smooth_exact(Ty, x=x, ysmooth=ys, want_var=False)),
                      ("smooth_exact, var", lambda: bank.smooth_exact(Ty, x=x, ysmooth=ys, var=var)),
                      ("one plane write", lambda: var.fill_(1.0))]
+        if a.posterior:
+            Tyg = Ty.clone()
+            Tyg[torch.rand((a.L, a.T), device="cuda") < 0.01] = float("nan")
+            legs += [("posterior, gap-free", lambda: bank.posterior(Ty, x=x, mean=ys, var=var)),
+                     ("posterior, 1 % missing", lambda: bank.posterior(Tyg, x=x, mean=ys, var=var))]
         print(f"status != 0: {int((status != 0).sum())} latents; var_smoothed / var_filtered in [{np.min(vs / vf):.3f}, {np.max(vs / vf):.3f}]")
         mb = a.L * a.T * es / 1e6
         for cold, (name, call) in [(c, leg) for c in (False, True) for leg in legs]:
