@@ -159,7 +159,7 @@ public:
         _obj->bfgs_mat = _solver->getBFGSMat();                                                     // :182
         _obj->oldparams = _params;                                                                  // :183
         double fx;
-        _solver->minimize(*_obj, _params, fx, _lb, _ub);                                            // :185
+        last_iterations = _solver->minimize(*_obj, _params, fx, _lb, _ub);                          // :185
         return yhat;
     }
 
@@ -176,6 +176,7 @@ public:
 
     Vector x;      // [L][d]
     Vector dx;     // [L][P][d]
+    int last_iterations = 0;      // of the last step()'s solve (not in the reference)
 
 private:
     MOIHGP<StateSpace>* _moihgp;

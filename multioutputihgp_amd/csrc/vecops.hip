@@ -71,7 +71,10 @@ __global__ void __launch_bounds__(kRedThreads) proj_grad_kernel(size_t n, const 
     __shared__ double red[kRedThreads / 64];
     double acc = 0.0;
     for (size_t i = (size_t)blockIdx.x * kRedThreads + threadIdx.x; i < n; i += (size_t)kRedBlocks * kRedThreads) {
-        const double d = fabs(fmin(fmax(x[i] - g[i], lb[i]), ub[i]) - x[i]);
+        double v = x[i] - g[i];                            // (compare-and-select, not fmax / fmin: those return the bound for a NaN, and a NaN gradient must not pass for a small one)
+        v = v < lb[i] ? lb[i] : v;
+        v = v > ub[i] ? ub[i] : v;
+        const double d = fabs(v - x[i]);
         acc = (d > acc || d != d) ? d : acc;
     }
     const double r = block_max(acc, red);

@@ -8,7 +8,14 @@
 //              -> RegressionObjective at params0 (apply_params), then predict()
 //   online_dev M L kern dt gamma W nticks | params0[np] | Y[nticks][M]
 //              -> the host learner and the device-vector learner (lbfgsb_dev.hpp) side by side from the same parameters: per tick both yhat,
-//                 then both parameter vectors, iteration counts and final objective values
+//                 then both parameter vectors, the device learner's last iteration count and objective value, and the iteration counts of
+//                 every tick (host's line, then the device learner's)
+//   objective_dev M L kern dt gamma W nticks npairs | params0[np] | p1[np] | p2[np] | Y[nticks][M] | npairs x (s[np] | y[np])
+//              -> OnlineObjectiveDev (lbfgsb_dev.hpp) and, on a second handle, the host OnlineObjective, both with the `npairs` correction
+//                 pairs in their BFGS matrix (m = 4; none: the empty matrix): the parameters after update(params0); which branch the
+//                 window takes ("batched" / "per_tick"); then at p1, p2, p1, p1 and -- after invalidate_update_cache() -- p2:
+//                 device loss | device gradient | host loss | host gradient | "device updates_skipped, host's evaluations";
+//                 last the proximal term alone (objectives without a window) at p1: device loss | gradient | host loss | gradient
 //   eigenlike  M L kern dt | params0[np] | y[M] ma[M]
 //              -> the reference learner's call pattern with an Eigen-like vector library (tests/cxx/eigen_like.hpp)
 #include <cstdio>
@@ -68,14 +75,69 @@ template <class SS> int online_dev_mode(size_t M, size_t L, double dt) {
     Vec p0(host.getNumParam()), y(M);
     if (!rd(p0)) return 2;
     host.setParams(p0); dev.setParams(p0);
+    std::vector<int> ith, itd;
     for (int t = 0; t < nt; t++) {
         if (!rd(y)) return 2;
         Vec a = host.step(y), b = dev.step(y);
         pr(a); pr(b);
+        ith.push_back(host.last_iterations); itd.push_back(dev.last_iterations);
     }
     Vec ph = host.getParams(), pd = dev.getParams();
     pr(ph); pr(pd);
     printf("%d %.17g\n", dev.last_iterations, dev.last_fx);
+    for (int v : ith) printf("%d ", v); printf("\n");
+    for (int v : itd) printf("%d ", v); printf("\n");
+    return 0;
+}
+template <class SS> int objective_dev_mode(size_t M, size_t L, double dt) {
+    double gamma; size_t W; int nt, npairs;
+    if (scanf("%lf %zu %d %d", &gamma, &W, &nt, &npairs) != 4) return 2;
+    moihgp::MOIHGP<SS> gpd(dt, M, L, false), gph(dt, M, L, false);
+    const size_t np = gpd.getNumParam();
+    Vec p0(np), p1(np), p2(np), y(M), s(np), yy(np);
+    if (!rd(p0) || !rd(p1) || !rd(p2)) return 2;
+    gpd.update(p0); gph.update(p0);
+    moihgp::opt::DevOps ops;
+    moihgp::OnlineObjectiveDev<SS> objd(&gpd, &ops, gamma, W), proxd(&gpd, &ops, gamma, W);       // (both read oldparams off the handle now)
+    moihgp::OnlineObjective<SS> objh(&gph, gamma, W), proxh(&gph, gamma, W);
+    pr(gpd.getParams());
+    for (int t = 0; t < nt; t++) { if (!rd(y)) return 2; objd.push_back(y); objh.push_back(y); }
+    if (npairs > 0) {
+        objh.bfgs_mat.reset((int)np, 4); objd.bfgs_mat.reset(&ops, np, 4);
+        moihgp::opt::DVec ds, dy;
+        for (int k = 0; k < npairs; k++) {
+            if (!rd(s) || !rd(yy)) return 2;
+            objh.bfgs_mat.add_correction(s, yy);
+            ops.upload(s, ds); ops.upload(yy, dy);
+            objd.bfgs_mat.add_correction(ds, dy);
+        }
+        proxh.bfgs_mat = objh.bfgs_mat; proxd.bfgs_mat = objd.bfgs_mat;
+    }
+    {   // which branch the window takes: the objectives ask moihgp_window_set the same question with the same centred window
+        Vec flat;
+        for (auto& yt : objh.Y) for (size_t m = 0; m < M; m++) flat.push_back(yt[m] - objh.ma[m]);
+        const int rc = moihgp_window_set(gph.handle(), flat.data(), objh.Y.size());
+        if (rc != 0 && rc != 3) return 3;
+        printf("%s\n", rc == 3 ? "per_tick" : "batched");
+    }
+    moihgp::opt::DVec dp, dg;
+    size_t host_evals = 0;
+    auto both = [&](moihgp::OnlineObjectiveDev<SS>& od, moihgp::OnlineObjective<SS>& oh, const Vec& p) {
+        Vec gd, gh;
+        ops.upload(p, dp);
+        const double ld = od(dp, dg);
+        ops.download(dg, gd);
+        const double lh = oh(p, gh);
+        host_evals++;
+        printf("%.17g\n", ld); pr(gd); printf("%.17g\n", lh); pr(gh);
+    };
+    const Vec* seq[5] = {&p1, &p2, &p1, &p1, &p2};
+    for (int k = 0; k < 5; k++) {
+        if (k == 4) { objd.invalidate_update_cache(); objh.invalidate_update_cache(); }
+        both(objd, objh, *seq[k]);
+        printf("%zu %zu\n", objd.updates_skipped, host_evals);
+    }
+    both(proxd, proxh, p1);
     return 0;
 }
 template <class SS> int regression_mode(size_t M, size_t L, double dt) {
@@ -136,6 +198,7 @@ int main() {
         if (!strcmp(mode, "objective")) return DISPATCH(objective_mode);
         if (!strcmp(mode, "online")) return DISPATCH(online_mode);
         if (!strcmp(mode, "online_dev")) return DISPATCH(online_dev_mode);
+        if (!strcmp(mode, "objective_dev")) return DISPATCH(objective_dev_mode);
         if (!strcmp(mode, "regression")) return DISPATCH(regression_mode);
         if (!strcmp(mode, "eigenlike")) return DISPATCH(eigenlike_mode);
     } catch (const std::exception& e) { fprintf(stderr, "%s\n", e.what()); return 3; }

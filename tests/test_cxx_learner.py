@@ -11,32 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT, rel_err
-
-BUILD = os.path.join(ROOT, "build")
-
-
-def _cxx(name, hip_built=None):
-    os.makedirs(BUILD, exist_ok=True)
-    exe = os.path.join(BUILD, name)
-    cmd = ["g++", "-std=c++14", "-O1", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "tests", "cxx"),
-           os.path.join(ROOT, "tests", "cxx", name + ".cpp"), "-o", exe]
-    if hip_built:
-        libdir = os.path.dirname(hip_built)
-        cmd += ["-L", libdir, "-lmoihgp", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"]
-    subprocess.run(cmd, check=True)
-    return exe
-
-
-def _fmt(a):
-    return " ".join(repr(float(v)) for v in np.asarray(a, dtype=np.float64).ravel())
-
-
-def _lines(exe, inp):
-    return subprocess.run([exe], input=inp, capture_output=True, text=True, check=True).stdout.strip().split("\n")
-
-
-def _arr(line):
-    return np.array(line.split(), dtype=float)
+from cxx_support import _arr, _cxx, _fmt, _lines
 
 
 # ------------------------------------------------------------------------------------------ CPU
@@ -95,9 +70,27 @@ def _params(M, L, rng):
                            np.column_stack([rng.uniform(0.5, 2, L), rng.uniform(0.5, 2, L), rng.uniform(0.05, 0.2, L)]).ravel()])
 
 
-def _online_objective_oracle(ref, gamma, W, p0, probe, Yticks):
+def _two_loop(pairs, v, a):
+    """a H v of BFGSMat::apply_Hv (LBFGSpp/BFGSMat.h:151-178) in long double: two-loop recursion over the (s, y) pairs, oldest first,
+    H0 = I / theta with theta = y.y / s.y of the newest pair."""
+    ld = np.longdouble
+    pairs = [(np.asarray(s, ld), np.asarray(y, ld)) for s, y in pairs]
+    r = ld(a) * np.asarray(v, ld)
+    alpha = []
+    for s, y in reversed(pairs):
+        alpha.append(s @ r / (s @ y))
+        r = r - alpha[-1] * y
+    s, y = pairs[-1]
+    r = r / ((y @ y) / (s @ y))
+    for (s, y), al in zip(pairs, reversed(alpha)):
+        r = r + (al - y @ r / (s @ y)) * s
+    return r.astype(np.float64)
+
+
+def _online_objective_oracle(ref, gamma, W, p0, probe, Yticks, pairs=None, oldparams=None):
     """moihgp_online.h:40-93 restated over the oracle object `ref` (already updated with p0): push_back every tick, then the
-    objective at `probe` with an empty BFGS matrix (Bp = dparams)."""
+    objective at `probe` with an empty BFGS matrix (Bp = dparams) or, given correction `pairs`, with Bp = gamma H dparams (:45-48).
+    `oldparams`: the parameters the objective was built at, for a second evaluation (by then `ref` holds the first one's)."""
     L, d, P, M = ref.L, ref.igp_dim, ref.num_igp_param, ref.M
     Y = []
     _x, _dx = np.zeros((L, d)), np.zeros((L, P, d))
@@ -108,11 +101,13 @@ def _online_objective_oracle(ref, gamma, W, p0, probe, Yticks):
         while len(Y) > W:
             Y.pop(0)
             _x, _dx = ref.step2(_x, Y[0] - ma, _dx)
-    oldparams = ref.params.copy()                                 # :31 (getParams at construction, after update(p0))
+    if oldparams is None:
+        oldparams = ref.params.copy()                             # :31 (getParams at construction, after update(p0))
     dparams = probe - oldparams
     ref.update(probe)                                             # :43
-    loss = 0.5 * dparams @ dparams                                # :51-53
-    grad = dparams.copy()
+    Bp = _two_loop(pairs, dparams, gamma) if pairs else dparams   # :45-51
+    loss = 0.5 * dparams @ Bp                                     # :53
+    grad = Bp.copy()
     x, dx = _x.copy(), _dx.copy()
     for yt in Y:                                                  # :61-70
         y = yt - ma
@@ -235,3 +230,152 @@ def test_cxx_device_vector_learner_follows_the_host_learner(hip_built, kern, M, 
     ph, pd = _arr(out[2 * nt]), _arr(out[2 * nt + 1])
     assert rel_err(pd, ph) < 1e-6
     assert np.abs(ph - p0).max() > 1e-4                                # the learner moved
+
+
+# ------------------------------------------------------------------------------------------ the device-resident objective
+def _blocks(M, L):
+    """The gradient's blocks: U, S, sigma, then one per latent (magnitude, lengthscale, noise)."""
+    nu = M * L
+    return [("U", slice(0, nu)), ("S", slice(nu, nu + L)), ("sigma", slice(nu + L, nu + L + 1))] + \
+           [(f"latent {l}", slice(nu + L + 1 + 3 * l, nu + L + 4 + 3 * l)) for l in range(L)]
+
+
+def _assert_blocks(got, want, M, L, tol, what):
+    """Every block to `tol` of its own largest reference entry: a whole-vector norm would hide the small blocks."""
+    worst = 0.0
+    for name, sl in _blocks(M, L):
+        scale = np.abs(want[sl]).max()
+        err = np.abs(got[sl] - want[sl]).max()
+        worst = max(worst, err / (tol * scale))
+        assert err <= tol * scale, (what, name, err, scale)
+    return worst
+
+
+def _objective_dev_run(exe, kern, M, L, W, p0, p1, p2, Y, pairs):
+    inp = f"objective_dev {M} {L} {0 if kern == 'Matern32' else 1} 0.1 0.9 {W} {len(Y)} {len(pairs)}\n" + \
+          "\n".join(_fmt(v) for v in [p0, p1, p2, *Y] + [v for sy in pairs for v in sy]) + "\n"
+    out = _lines(exe, inp)
+    evals = []
+    for k in range(6):                                            # p1, p2, p1, p1, p2 after invalidate; then the proximal term alone at p1
+        o = 2 + 5 * k
+        evals.append(dict(loss_d=float(out[o]), grad_d=_arr(out[o + 1]), loss_h=float(out[o + 2]), grad_h=_arr(out[o + 3]),
+                          skipped=int(out[o + 4].split()[0]) if k < 5 else None))
+    return _arr(out[0]), out[1], evals
+
+
+OBJECTIVE_SHAPES = [("Matern32", 5, 2, 3, 7), ("Matern52", 7, 4, 4, 4), ("Matern52", 6, 3, 1, 5), ("Matern52", 9, 5, 3, 6)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kern,M,L,W,nt", OBJECTIVE_SHAPES)
+def test_cxx_device_objective_vs_oracle(hip_built, kern, M, L, W, nt):
+    """OnlineObjectiveDev (and the host OnlineObjective next to it) against the oracle's restatement: loss to 1e-9, the gradient block by
+    block to 1e-8 of each block's own largest entry; with an empty BFGS matrix and with three correction pairs in it (gamma = 0.9), for
+    which the proximal term alone is also held to 1e-12 of a long-double two-loop recursion.  The update cache: evaluations at p1, p2, p1,
+    p1 and, after invalidate_update_cache(), p2 skip 0, 0, 0, 1, 1 updates, each equals the oracle at its own parameters (no stale
+    handle), and the repeated p1 is bit-equal."""
+    from oracle import cref
+    exe = _cxx("learner_test", hip_built)
+    rng = np.random.default_rng(100 * M + L + W)
+    ref = cref.GP(0.1, M, L, kern); ref.set_literal_ugrad(0)
+    p0 = _params(M, L, rng)
+    ref.update(p0)
+    old = ref.params.copy()
+    probes = []
+    for _ in range(2):
+        p = old + 0.01 * rng.standard_normal(ref.num_param)
+        p[M * L:] = np.abs(p[M * L:])
+        probes.append(p)
+    p1, p2 = probes
+    Y = 0.5 * rng.standard_normal((nt, M)) + 1.0
+    pairs = []
+    for _ in range(3):
+        s = 0.01 * rng.standard_normal(ref.num_param)
+        pairs.append((s, s * rng.uniform(0.5, 2.0, ref.num_param) + 0.001 * rng.standard_normal(ref.num_param)))
+    assert all(s @ y > 0 for s, y in pairs)
+    for use in ([], pairs):
+        got_old, branch, ev = _objective_dev_run(exe, kern, M, L, W, p0, p1, p2, list(Y), use)
+        assert rel_err(got_old, old) < 1e-10 and branch == "batched"
+        assert [e["skipped"] for e in ev[:5]] == [0, 0, 0, 1, 1]
+        worst = 0.0
+        for k, p in enumerate([p1, p2, p1, p1, p2]):
+            ref.update(p0)                                        # (the window was pushed, and its start state carried, under p0)
+            loss, grad, _, nY = _online_objective_oracle(ref, 0.9, W, p0, p, list(Y), pairs=use, oldparams=old)
+            assert nY == min(W, nt)
+            for side in "dh":
+                assert abs(ev[k]["loss_" + side] - loss) < 1e-9 * abs(loss), (k, side)
+                worst = max(worst, _assert_blocks(ev[k]["grad_" + side], grad, M, L, 1e-8, (k, side)))
+        for side in "dh":                                         # the second of two evaluations at p1 in a row skipped its update: same bits
+            assert ev[3]["loss_" + side] == ev[2]["loss_" + side] and np.array_equal(ev[3]["grad_" + side], ev[2]["grad_" + side])
+        dp = p1 - old                                             # the proximal term alone
+        Bp = _two_loop(use, dp, 0.9) if use else dp
+        for side in "dh":
+            assert abs(ev[5]["loss_" + side] - 0.5 * dp @ Bp) <= 1e-12 * abs(0.5 * dp @ Bp), side
+            assert np.abs(ev[5]["grad_" + side] - Bp).max() <= 1e-12 * np.abs(Bp).max(), side
+        print(f"{kern} M={M} L={L} W={W}, {len(use)} pairs: worst gradient block error / bar {worst:.3g}")
+
+
+@pytest.mark.gpu
+def test_cxx_device_objective_window_beyond_the_batched_limits(hip_built):
+    """Two outputs of four missing in one tick with L = 3: moihgp_window_set answers 3 and both objectives walk the window tick by tick.
+    They agree on which entries are NaN; the finite ones -- the per-latent blocks -- match a Python loop over the per-tick ABI
+    (gp32_lik1 / gp32_step2) to 1e-8 of their block's scale."""
+    from multioutputihgp_amd import MOIHGP
+    kern, M, L, W, nt = "Matern32", 4, 3, 4, 3
+    exe = _cxx("learner_test", hip_built)
+    rng = np.random.default_rng(5)
+    p0 = _params(M, L, rng)
+    gp = MOIHGP(0.1, M, L, kernel="Matern32")
+    gp.update(p0)
+    old = np.array(gp.params, dtype=np.float64)
+    p1 = old + 0.01 * rng.standard_normal(old.size)
+    p1[M * L:] = np.abs(p1[M * L:])
+    Y = 0.5 * rng.standard_normal((nt, M)) + 1.0
+    Y[1, [0, 2]] = np.nan
+    got_old, branch, ev = _objective_dev_run(exe, kern, M, L, W, p0, p1, p1, list(Y), [])
+    assert rel_err(got_old, old) < 1e-10 and branch == "per_tick"
+    gp.update(p1)
+    Yc = Y - Y.mean(axis=0)                                       # (the window mean of an output with a missing tick is NaN, as in the learner)
+    x, dx = np.zeros((L, gp.igp_dim)), np.zeros((L, gp.num_igp_param, gp.igp_dim))
+    loss, grad = 0.5 * (p1 - old) @ (p1 - old), p1 - old
+    for y in Yc:
+        l, g = gp.negLogLikelihood(x, y, dx)
+        loss, grad = loss + l, grad + g
+        x, dx = gp.step_no_yhat(x, y, dx)
+    nan = np.isnan(grad)
+    lat = slice(M * L + L + 1, None)
+    assert not nan[lat].any() and nan.any()
+    for side in "dh":
+        g = ev[0]["grad_" + side]
+        assert np.array_equal(np.isnan(g), nan), side
+        assert np.isnan(ev[0]["loss_" + side]) == np.isnan(loss) and (np.isnan(loss) or abs(ev[0]["loss_" + side] - loss) < 1e-9 * abs(loss)), side
+        for name, sl in _blocks(M, L)[3:]:
+            assert np.abs(g[sl] - grad[sl]).max() <= 1e-8 * np.abs(grad[sl]).max(), (side, name)
+        if (~nan[:M * L + L + 1]).any():                          # whatever else is finite
+            f = ~nan
+            assert np.abs(g[f] - grad[f]).max() <= 1e-8 * np.abs(grad[f]).max(), side
+
+
+@pytest.mark.gpu
+def test_cxx_device_vector_learner_with_active_bounds(hip_built):
+    """The learners from parameters on their box: two lengthscales on lb = 1e-4 and sigma on ub = 1e2, so that the active set is not
+    trivial, `proj_step` clamps and the masked two-loop recursion sees a real mask.  What the interior test asserts, and the same
+    iteration count in both learners at every tick."""
+    kern, M, L, W, nt = 0, 6, 3, 4, 8
+    exe = _cxx("learner_test", hip_built)
+    rng = np.random.default_rng(23)
+    p0 = _params(M, L, rng)
+    p0[M * L + L] = 1e2                                            # sigma on its upper bound
+    p0[M * L + L + 1 + 3 * 0 + 1] = p0[M * L + L + 1 + 3 * 1 + 1] = 1e-4      # lengthscales of latents 0 and 1 on their lower bound
+    t = np.arange(nt)[:, None]
+    Y = np.sin(0.3 * t + np.arange(M)[None, :]) + 0.05 * rng.standard_normal((nt, M))
+    out = _lines(exe, f"online_dev {M} {L} {kern} 0.1 0.9 {W} {nt}\n{_fmt(p0)}\n" + "\n".join(_fmt(y) for y in Y) + "\n")
+    for k in range(nt):
+        a, b = _arr(out[2 * k]), _arr(out[2 * k + 1])
+        assert np.all(np.isfinite(a)) and rel_err(b, a) < 1e-7, k
+    ph, pd = _arr(out[2 * nt]), _arr(out[2 * nt + 1])
+    assert rel_err(pd, ph) < 1e-6
+    assert np.abs(ph - p0).max() > 1e-4                                # the learner moved
+    ith, itd = [int(v) for v in out[2 * nt + 3].split()], [int(v) for v in out[2 * nt + 4].split()]
+    assert len(ith) == nt and ith == itd and max(ith) >= 1
+    print("iterations per tick", ith, "positive parameters on a bound at the end", int(((ph[M * L:] <= 1e-4) | (ph[M * L:] >= 1e2)).sum()))
