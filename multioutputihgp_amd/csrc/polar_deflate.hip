@@ -316,7 +316,7 @@ size_t polar_deflate_work_doubles(size_t M, size_t L) {
 }
 
 // X (M x L, device) with Gram matrix G (L x L, device) = X^T X and frob2 = ||G - I||_F^2.  On success *n_pairs pairs were deflated: when > 0,
-// X and G are both updated in place (G <- W G W by three rank-NB terms, not by a new product).  Returns 0, or a HIP / launch error code.
+// X and G are both updated in place (G <- W G W by three rank-NB terms, not by a new product, unless a deflated singular value lies below 1 / sqrt 2).  Returns 0, or a HIP / launch error code.
 // *warm (in / out, may be NULL): non-zero on entry = `work` still holds the Ritz vectors of the previous successful call for the same (M, L) --
 // consecutive objective evaluations of a learner differ by one line-search step, and so do their outlying subspaces: the iteration starts from
 // them instead of the random block (one pass fewer).  Set on return according to whether Ritz vectors were left behind.
@@ -394,6 +394,7 @@ int polar_deflate(double* X, size_t M, size_t L, double* G, double frob2, double
             if (fabs(h_d[i]) > 1e-13) worst = fmax(worst, crit);
             n_ok += accept[i] ? 1 : 0;
         }
+        // (tests/test_polar_factor.py parses this line -- pass number, "(warm start)", captured, converged pairs: keep its format)
         if (trace) std::fprintf(stderr, "polar: deflation pass %d%s  |lambda|max %.4e  captured %.4f of ||E||_F^2  worst |d| res %.2e (tol %.1e)  converged pairs %d\n",
                                 it + 1, warm_start ? " (warm start)" : "", lmax, energy / frob2, worst, tolc, n_ok);
         if ((it >= 1 || warm_start) && energy < 0.9 * frob2) {           // E is not a few directions: nothing to gain here
@@ -416,14 +417,23 @@ int polar_deflate(double* X, size_t M, size_t L, double* G, double frob2, double
         }
     }
     if (n_ok == 0) return 0;
-    for (int i = 0; i < NB; i++) if (!accept[i]) h_d[i] = 0.0;
+    double g1min = 1.0;                                                   // the smallest accepted eigenvalue 1 + lambda_i of G
+    for (int i = 0; i < NB; i++) { if (!accept[i]) h_d[i] = 0.0; else g1min = fmin(g1min, 1.0 + h_lam[i]); }
     MOIHGP_HIP_FATAL(hipMemcpyAsync(dvec, h_d, sizeof(double) * NB, hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL((ts_mm_kernel<false>), dim3((unsigned)((M + 15) / 16)), dim3(256), 0, s, (const double*)X, L, M, L, (const double*)Wm, P);    // P = A W
     hipLaunchKernelGGL(rank_update_kernel, dim3((unsigned)((L + 255) / 256), (unsigned)((M + 31) / 32)), dim3(256), 0, s, X, M, L, (const double*)P, (const double*)dvec,
                        (const double*)Wm);
-    // G <- W G W: the Gram matrix of the updated X (polar.hip continues from it)
-    hipLaunchKernelGGL(gram_update_kernel, dim3((unsigned)((L + 255) / 256), (unsigned)((L + 31) / 32)), dim3(256), 0, s, G, L, (const double*)Wm, (const double*)YZ,
-                       (const double*)dvec, (const double*)lam);
+    // G <- W G W: the Gram matrix of the updated X (polar.hip continues from it).  The three rank-NB terms take d_i from 1 + lambda_i, which for
+    // a singular value well below 1 is a difference of nearly equal numbers: known to eps in absolute terms, to eps / sigma_i^2 in relative ones.
+    // The deflated singular value is then 1 + O(eps / sigma_i^2) while this G, built from the same d_i, says 1 exactly -- and the iteration,
+    // which steps by G, never sees the difference (sigma = 1e-4: U^T U off by 5e-8).  Below sigma^2 = 1/2 G is formed from X again instead:
+    // at and above that threshold the relative loss eps / sigma_i^2 is at most 2 eps, one bit, so the formula is as good as a new product
+    // there (a judgement, not a tuned figure); below it one L x L x M product is paid, which the learner's spectrum (sigma >= 0.999) never is.
+    if (g1min < 0.5) {
+        if (int rc = launch_gram(X, M, L, G, s)) return rc;
+    } else
+        hipLaunchKernelGGL(gram_update_kernel, dim3((unsigned)((L + 255) / 256), (unsigned)((L + 31) / 32)), dim3(256), 0, s, G, L, (const double*)Wm, (const double*)YZ,
+                           (const double*)dvec, (const double*)lam);
     if (int rc = check_launch("polar_deflate (update)")) return rc;
     MOIHGP_HIP_FATAL(hipStreamSynchronize(s));                            // (h_d is on this frame's stack)
     *n_pairs = n_ok;

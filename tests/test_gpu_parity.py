@@ -485,8 +485,8 @@ def test_polar_factor_spectra_with_outliers(env, M, L, shape, monkeypatch):
     assert rel_err(U, u @ vt) < 1e-10, (shape, its)
     if shape in ("learner", "one_small"):
         assert 0 < its <= 3, its
-    # the same without the deflation: same factor
-    monkeypatch.setenv("MOIHGP_POLAR_DEFLATE", "0")
+    # (the same without the deflation -- MOIHGP_POLAR_DEFLATE=0, read once per process -- runs in a child process of test_polar_factor.py:
+    # test_plain_newton_schulz_on_the_same_spectra)
 
 
 def test_polar_factor_rank_deficient_input_is_reported(env, capfd):
